@@ -6,8 +6,21 @@ One step = one NnetCtcUpdater::ComputeForMinibatch with SGD
 [CuDNNRecurrent -> ClipGradient(30)] x 5 -> Affine(41)) on a synthetic
 minibatch of N=16 utterances, T_max=2000, 40-dim features (BASELINE.md §2
 generator, seed 20161015 + 1000*rank + step), fp32.  Inputs are resident in
-HBM when the timed region starts (a second pass with the H2D copy inside
-every step is reported beside it).  frames = sum of real frames T_n.
+HBM when the timed region starts.  frames = sum of real frames T_n.
+
+A plain run (`--gpus G --steps K --warmup W`) sets up, warms up, times the K
+steps (`value`, `ms_per_step`), writes its outputs if `--dump-outputs DIR` is
+given and prints the result line; nothing else.  `--full` adds everything
+else described below (loss match, the profiled and H2D-inclusive passes, the
+rooflines, the CPU baseline); its `--no-*` switches drop single legs.
+
+`--dump-outputs DIR` writes what the last timed step of the `value` pass
+returned and left in the trainer, as DIR/<name>.npy (float32 / float64):
+the (objf, accuracy, weight) stats of every timed step, the last minibatch's
+per-utterance costs, network output and best path, and the parameters after
+and the gradient of the last update of every updatable component.  Arrays
+above a size cap are a fixed, seeded sample of their entries (the same
+entries for the same arguments), so two builds compare output for output.
 
 Multi-GPU: one process per GPU; each rank trains its own N=16 shard and the
 weight gradients are summed with RCCL (kctc_nnet_enable_dp), so per-GPU work
@@ -19,13 +32,14 @@ before anything touches the GPU; under torch.distributed.run it is one rank.
 CU-masked share of it (kctc_set_cu_partition) -- a rehearsal of the N-rank
 path on a one-GPU box, not a throughput configuration.
 
-Before the timed region the bench checks the loss: one train step of the
+With `--full`, after the timed passes the bench checks the loss: one train step of the
 committed full-size fixture of the measured config (tests/golden/
 sketch_step*.npz, fp64 oracle, same parameters and minibatch) must match at
 1e-4 -- configs[4] (bf16 operands) at its error model's per-output bar
 (tests/sketch_common.py) -- (`loss_match`).
 
-Three timed passes of K steps each, all after the warm-up:
+With `--full`, three timed passes of K steps each, all after the warm-up (a
+plain run makes the first only):
   1. `value`: HBM-resident features, no profiling events (the measurement
      contract: inputs resident when the timed region starts; the trainer's
      boundary takes device features);
@@ -36,8 +50,8 @@ Three timed passes of K steps each, all after the warm-up:
      step -- SURVEY §8d's timed region, which starts at the H2D copy --
      reported beside `value` (the PCIe-inclusive rate is never `value`).
 
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (HIP
-events on the trainer's stream over the timed region) and a CPU baseline
+Prints ONE JSON line (rank 0); with `--full` it holds the roofline of the
+dominant kernel (HIP events on the trainer's stream over the timed region) and a CPU baseline
 (the oracle's fp32 restatement, OpenMP, on utterances of the GPU run's own
 first timed minibatch with the run's initial parameters; rank 0 at N=1 only).
 """
@@ -92,6 +106,11 @@ def parse_args(argv=None):
     ap.add_argument("--dp-transport", choices=("rccl", "host"), default="rccl",
                     help="N>1: gradient sum over RCCL (one GPU per rank) or gloo on the host "
                          "(ranks may share a GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: loss match, profiled pass and rooflines, H2D-inclusive "
+                         "pass, CPU baseline (each can be dropped with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-h2d-pass", action="store_true")
@@ -338,6 +357,50 @@ def cpu_baseline(params0, batch, T, D, H, A, L, ratio=0.125, mode=2, Ns=4):
                       f"the run's initial parameters) in {dt:.1f}s"}
 
 
+# ---- output dump ------------------------------------------------------------------
+DUMP_SEED = 20161015
+DUMP_MAX_PARAM = 1 << 19   # sampled entries of one component's parameters / gradient
+DUMP_MAX_OUTPUT = 1 << 23  # of the network output (float32: 32 MB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample(a, max_elems, tag):
+    """`a` flattened as float32 / float64; above max_elems a fixed sample of
+    its entries (sorted indices drawn without replacement from a generator
+    seeded by DUMP_SEED, the array's size and `tag`: the same entries for the
+    same arguments on every run and every build)."""
+    a = np.asarray(a)
+    if a.dtype != np.float64:
+        a = a.astype(np.float32)
+    if a.size <= max_elems:
+        return np.ascontiguousarray(a)
+    rng = np.random.default_rng([DUMP_SEED, a.size, tag])
+    idx = np.sort(rng.choice(a.size, size=max_elems, replace=False))
+    return np.ascontiguousarray(a.reshape(-1)[idx])
+
+
+def collect_outputs(net, stats, T, N, A, updatable):
+    """What the timed path's last step returned and left in the trainer (see
+    the module docstring), name -> array."""
+    out = {"step_stats": np.array(stats, np.float64).reshape(-1, 3),
+           "costs": net.last_costs(N),
+           "logits": dump_sample(net.last_output(T, N, A), DUMP_MAX_OUTPUT, 1),
+           "best_path": dump_sample(net.last_best_path(T, N), DUMP_MAX_OUTPUT // 8, 2)}
+    for i in updatable:
+        out[f"params_c{i}"] = dump_sample(net.get_params(i), DUMP_MAX_PARAM, 100 + i)
+        out[f"grad_c{i}"] = dump_sample(net.get_grad(i), DUMP_MAX_PARAM, 200 + i)
+    return out
+
+
+def write_outputs(dirname, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -370,7 +433,12 @@ def main():
     if bf16:
         net.set_precision("bf16")
     rnn_idx = [1 + 2 * c for c in range(L)]
-    params0 = ([net.get_params(i) for i in rnn_idx], net.get_params(2 * L + 1))
+    # a plain run does what `value` needs; the other legs are --full's
+    profile = args.full and not args.no_profile
+    h2d_pass = args.full and not args.no_h2d_pass
+    want_loss_match = args.full and not args.no_loss_match
+    want_cpu = args.full and not args.no_cpu_baseline and rank == 0 and world == 1
+    params0 = ([net.get_params(i) for i in rnn_idx], net.get_params(2 * L + 1)) if want_cpu else None
     dp_info = None
     if world > 1:
         if args.average_every > 0:
@@ -397,8 +465,9 @@ def main():
     batches, host_batches = [], []
     for step in range(total):
         feats, nf, fl, ll = k.synth_minibatch(20161015 + 1000 * rank + step, T, N, D, A, ratio)
-        batches.append((torch.from_numpy(feats).to(dev), nf, fl, ll, torch.from_numpy(feats).pin_memory()))
-        host_batches.append((feats, nf, fl, ll) if step == args.warmup else None)
+        batches.append((torch.from_numpy(feats).to(dev), nf, fl, ll,
+                        torch.from_numpy(feats).pin_memory() if h2d_pass else None))
+        host_batches.append((feats, nf, fl, ll) if want_cpu and step == args.warmup else None)
     torch.cuda.synchronize()
 
     warm_stats = []
@@ -406,7 +475,6 @@ def main():
         f, nf, fl, ll, _ = batches[step]
         warm_stats.append(net.train_step(f, T, N, nf, fl, ll))
 
-    profile = not args.no_profile
     ext = torch.cuda.ExternalStream(net.stream, device=dev)
 
     def barrier():
@@ -450,7 +518,10 @@ def main():
 
     net.set_profiling(False)
     dt, frames, stats, step_ms = timed_pass(False)
-    traj = np.array([[o, w] for o, _, w in warm_stats + stats], np.float64)
+    if args.dump_outputs and rank == 0:
+        # here, before any further pass trains the model on
+        write_outputs(args.dump_outputs, collect_outputs(net, stats, T, N, A, rnn_idx + [2 * L + 1]))
+    traj =np.array([[o, w] for o, _, w in warm_stats + stats], np.float64)
     objf = sum(o for o, _, _ in stats)
     acc = sum(a for _, a, _ in stats)
     wt = sum(w for _, _, w in stats)
@@ -478,7 +549,7 @@ def main():
                 prof[fam] = (ms, n)
     net.set_profiling(False)
     h2d = None
-    if not args.no_h2d_pass:
+    if h2d_pass:
         dt2, frames2, _, step_ms2 = timed_pass(True)
         h2d = (dt2, frames2, step_ms2)
 
@@ -605,11 +676,11 @@ def main():
     # after the timed passes: with this second Nnet created and freed before
     # them, the trainer's recurrences ran 2-4 % slower (configs[1]: 727.8k vs
     # 752.2k frames/s, same box, profiles/r05e_lossmatch_ab.txt)
-    if rank == 0 and not args.no_loss_match and (T, N, H, L) == (cf["T"], cf["N"], cf["H"], 5):
+    if rank == 0 and want_loss_match and (T, N, H, L) == (cf["T"], cf["N"], cf["H"], 5):
         lm = loss_match(k, dev, {1: "cfg1", 2: "cfg2", 4: "cfg4"}[args.config])
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_cpu:
         cpu = cpu_baseline(params0, host_batches[args.warmup], T, D, H, A, L, ratio, mode=mode,
                            Ns=2 if H > 512 else 4)
 

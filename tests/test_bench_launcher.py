@@ -41,6 +41,26 @@ def test_args_defaults():
     assert (a.gpus, a.steps, a.warmup, a.config, a.dp_transport) == (1, 100, 3, 1, "rccl")
     a = bench.parse_args(["--gpus", "2", "--dp-transport", "host"])
     assert (a.gpus, a.dp_transport) == (2, "host")
+    # a plain run is lean: the other legs and the dump are asked for
+    assert (a.full, a.dump_outputs) == (False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert (a.full, a.dump_outputs) == (True, "d")
+
+
+def test_dump_sample_is_fixed(tmp_path):
+    import numpy as np
+    small = np.arange(10, dtype=np.int32)
+    s = bench.dump_sample(small, 16, 1)
+    assert s.dtype == np.float32 and np.array_equal(s, small)
+    big = np.arange(1000, dtype=np.float64).reshape(10, 100)
+    a, b = bench.dump_sample(big, 64, 7), bench.dump_sample(big.copy(), 64, 7)
+    assert a.dtype == np.float64 and a.shape == (64,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0)                           # distinct entries, in order
+    assert not np.array_equal(a, bench.dump_sample(big, 64, 8))
+    bench.write_outputs(str(tmp_path / "o"), {"x": a, "y": s})
+    assert np.array_equal(np.load(tmp_path / "o" / "x.npy"), a)
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "o"), {"ids": small})
 
 
 CHILD = r'''
