@@ -1811,20 +1811,35 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   // this element's operand columns as per-lane pointers, opaque to the
   // compiler: they stay in VGPRs and the kernel-argument bases die here
   // (the loop's scalar registers spill otherwise)
-  const float *dy_e = p.dy + (long)n * ldy + (long)d * H + u0 + eu;
-  const float *g_e = p.G + (long)n * ldg + (long)d * NW * H + u0 + eu;
-  const float *aux_e = p.aux + (long)n * ldy + (long)d * H + u0 + eu;
-  const float *prv_e = (MODE == kLstm ? p.aux : p.y) + (long)n * ldy + (long)d * H + u0 + eu;
-  asm volatile("" : "+v"(dy_e), "+v"(g_e), "+v"(aux_e), "+v"(prv_e));
-  auto prefetch = [&](int k) {  // operands of forward-order step k into n*
-    if (!live) return;
-    const int t = d == 0 ? k : T - 1 - k, tp = d == 0 ? t - 1 : t + 1;
-    const long yo = (long)t * N * ldy, go = (long)t * N * ldg, po = (long)tp * N * ldy;
-    ndy = dy_e[yo];
+  // They start at the first step's time (forward-order step T - 1) and move
+  // one step image per prefetch / row store (the loop's time moves by tstep
+  // frames a step): no per-step index arithmetic.  The laundering leaves
+  // generic pointers (FLAT loads, which count in lgkmcnt too, so that every
+  // LDS wait before a barrier covered the HBM loads): cast back to global
+  typedef const float __attribute__((address_space(1))) *gcfp;
+  typedef float __attribute__((address_space(1))) *gfp;
+  const int t_first = d == 0 ? T - 1 : 0;
+  const long ystep = (d == 0 ? -1 : 1) * (long)N * ldy, gstep = (d == 0 ? -1 : 1) * (long)N * ldg;
+  const long yel = ((long)t_first * N + n) * ldy + (long)d * H + u0 + eu;
+  const long gel = ((long)t_first * N + n) * ldg + (long)d * NW * H + u0 + eu;
+  const float *dy_e = p.dy + yel;
+  const float *g_e = p.G + gel;
+  const float *aux_e = p.aux + yel;
+  const float *prv_e = (MODE == kLstm ? p.aux : p.y) + yel + ystep;  // the step before, in forward order
+  float *e_e = p.E + gel;
+  float *dx_e = (MODE == kGru ? p.DX : p.E) + gel;
+  asm volatile("" : "+v"(dy_e), "+v"(g_e), "+v"(aux_e), "+v"(prv_e), "+v"(e_e), "+v"(dx_e));
+  gcfp dy_p = (gcfp)dy_e, g_p = (gcfp)g_e, aux_p = (gcfp)aux_e, prv_p = (gcfp)prv_e;
+  gfp e_p = (gfp)e_e, dx_p = (gfp)dx_e;
+  auto prefetch = [&](int k) {  // operands of forward-order step k (T - 1, T - 2, ... in turn) into n*
+    if (live) {
+      ndy = *dy_p;
 #pragma unroll
-    for (int q = 0; q < NW; q++) ng[q] = g_e[go + q * H];
-    na = aux_e[yo];
-    nap = k > 0 ? prv_e[po] : 0.f;
+      for (int q = 0; q < NW; q++) ng[q] = g_p[q * H];
+      na = *aux_p;
+      nap = k > 0 ? *prv_p : 0.f;
+    }
+    dy_p += ystep; g_p += gstep; aux_p += ystep; prv_p += ystep;
   };
   auto rotate = [&]() {
     cdy = ndy; ca = na; cap = nap;
@@ -1876,25 +1891,28 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
       }
     }
   };
-  auto e_store = [&](int t) {  // row-major dGates of step t (E; GRU also DX)
+  // row-major dGates of step t (E; GRU also DX): the loop's steps in turn,
+  // e_p / dx_p move on by one step image a call
+  auto e_store = [&](int t) {
+    const gfp ep = e_p, dp = dx_p;
+    e_p += gstep; dx_p += gstep;
     if (pk) {
       pk_store(t);
       return;
     }
     if (!live) return;
-    const long grow = ((long)t * N + n) * ldg + (long)d * NW * H + u0 + eu;
     if (p.e_sc1) {  // DX (== E for LSTM) went out through estg already
       if (MODE == kGru) {
 #pragma unroll
-        for (int q = 0; q < NW; q++) p.E[grow + q * H] = eg[q];
+        for (int q = 0; q < NW; q++) ep[q * H] = eg[q];
       }
       return;
     }
 #pragma unroll
-    for (int q = 0; q < NW; q++) p.E[grow + q * H] = eg[q];
+    for (int q = 0; q < NW; q++) ep[q * H] = eg[q];
     if (MODE == kGru) {
 #pragma unroll
-      for (int q = 0; q < NW; q++) p.DX[grow + q * H] = dxk[q];
+      for (int q = 0; q < NW; q++) dp[q * H] = dxk[q];
     }
   };
   // consumer chunk of this thread: position pos (of the own column tiles'
@@ -2552,10 +2570,25 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
     gin[q] = gnx[q] = act[q] = 0.f;
     bR[q] = (MODE == kGru && has_e) ? Wd[p.bR_off + q * H + u0 + eu] : 0.f;
   }
-  auto gin_load = [&](int t, float (&dst)[NW]) {
+  // Row-major addressing of the step loop: the element's byte offsets in a
+  // step's y / aux and G rows stay in two VGPRs (opaque to the compiler, or it
+  // works them out again every step), and the step's rows are wave-uniform
+  // bases (yrow, grow, arow below) moved by one step image a step with scalar
+  // adds -- no per-lane 64-bit index arithmetic between the last MFMA and the
+  // K-partial writes the workgroup's barrier waits for
+  typedef const float __attribute__((address_space(1))) *gcfp;
+  typedef float __attribute__((address_space(1))) *gfp;
+  unsigned yob = (unsigned)(((long)n * ldy + (long)d * H + u0 + eu) * sizeof(float));
+  unsigned gob = (unsigned)(((long)n * ldg + (long)d * NW * H + u0 + eu) * sizeof(float));
+  asm volatile("" : "+v"(yob), "+v"(gob));
+  auto at = [](const float *base, unsigned ob) {  // element at byte offset ob of a step's rows
+    return (gfp) reinterpret_cast<float *>(reinterpret_cast<uintptr_t>(base) + ob);
+  };
+  auto gin_load = [&](const float *gr, float (&dst)[NW]) {  // gr: the step's G rows
     if (!live) return;
+    const gcfp s = at(gr, gob);
 #pragma unroll
-    for (int q = 0; q < NW; q++) dst[q] = p.G[((long)t * N + n) * ldg + (long)d * NW * H + q * H + u0 + eu];
+    for (int q = 0; q < NW; q++) dst[q] = s[q * H];
   };
   // bf16_io: the step's h (stg, bf16 [16][U]) as packed rows and columns
   auto y_pk_store = [&](int tt) {
@@ -2583,15 +2616,16 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
       }
     }
   };
-  auto out_store = [&](int t) {  // row-major y, activations (in place of G), aux of step t
+  // row-major y, activations (in place of G), aux of a step, given its rows
+  auto out_store = [&](const float *yr, const float *gr, const float *ar) {
     if (!live) return;
-    if (p.ysc1) __hip_atomic_store(p.y + ((long)t * N + n) * ldy + (long)d * H + u0 + eu, hval, __ATOMIC_RELAXED,
+    if (p.ysc1) __hip_atomic_store(at(yr, yob), hval, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);  // read by other XCDs during this kernel
-    else p.y[((long)t * N + n) * ldy + (long)d * H + u0 + eu] = hval;
-    const long grow = ((long)t * N + n) * ldg + (long)d * NW * H + u0 + eu;
+    else *at(yr, yob) = hval;
+    const gfp gd = at(gr, gob);
 #pragma unroll
-    for (int q = 0; q < NW; q++) p.G[grow + q * H] = act[q];
-    p.aux[((long)t * N + n) * ldy + (long)d * H + u0 + eu] = cnew;
+    for (int q = 0; q < NW; q++) gd[q * H] = act[q];
+    *at(ar, yob) = cnew;
   };
   // IO waves: thread tid - 64 CW <-> element (ion, iou); G of step k into
   // ginl[k & 1] before step k's K-reduction barrier
@@ -2640,9 +2674,14 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
       io_wait();
     }
     __syncthreads();
-  } else {
-    gin_load(d == 0 ? 0 : T - 1, gin);
   }
+  // the rows of the loop's current step (time t): wave-uniform, one step
+  // image (tstep frames) on at the end of every step
+  const long ysl = (d == 0 ? 1 : -1) * (long)N * ldy, gsl = (d == 0 ? 1 : -1) * (long)N * ldg;
+  const float *yrow = p.y + (long)(d == 0 ? 0 : T - 1) * N * ldy;
+  const float *arow = p.aux + (long)(d == 0 ? 0 : T - 1) * N * ldy;
+  const float *grow = p.G + (long)(d == 0 ? 0 : T - 1) * N * ldg;
+  if constexpr (!IOW) gin_load(grow, gin);
   int bad = 0;
   unsigned *myflag = flag6(p, grp, d, g, NWG);
   // XCD-pinned (p.xpd): the hand-off goes through a ring of p.ring step images
@@ -2813,13 +2852,23 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
           }
         }
       }
+      if constexpr (!IOW) {
+        // this step's input projection row (loaded behind the last step's
+        // hand-off loads) moves in here: the first MFMA's wait for the
+        // hand-off loads has retired those older loads too (one in-order
+        // vmcnt), so the cell below does not wait for memory.  Rotated in
+        // the cell instead, the wait for them -- HBM misses -- and for the
+        // row stores issued with them stood between the cell's exp and rcp
+#pragma unroll
+        for (int q = 0; q < NW; q++) gin[q] = gnx[q];
+      }
     }
     asm volatile("" ::: "memory");
     // behind the hand-off loads: last step's row-major outputs, next step's input projection
-    if (!IO_OUT && t_prev >= 0) out_store(t_prev);
+    if (!IO_OUT && t_prev >= 0) out_store(yrow - ysl, grow - gsl, arow - ysl);
     // (stg still holds step t_prev's h: the cell phase below rewrites it)
     if (BF && p.yr && t_prev >= 0) y_pk_store(t_prev);
-    if (!IOW && k + 1 < T) gin_load(d == 0 ? t + 1 : t - 1, gnx);
+    if (!IOW && k + 1 < T) gin_load(grow + gsl, gnx);
     // K partials through LDS.  U % 16 == 0: column ct * 16 + fr of the
     // tile is gate ct / (U / 16) of unit (ct % (U / 16)) * 16 + fr, so a lane
     // holds every gate of its (row, unit) elements: one float4 per (wave,
@@ -2898,12 +2947,6 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
       }
       if (!live) h = 0.f;
       hval = h;
-      if constexpr (!IOW) {
-        // the next step's input projection (loaded behind this step's
-        // hand-off loads) moves in here
-#pragma unroll
-        for (int q = 0; q < NW; q++) gin[q] = gnx[q];
-      }
       if constexpr (IO_OUT) {  // outputs for the IO waves (stored during the next step)
         float *o = outl + (long)(k & 1) * (NW + 2) * 16 * U + tid;
         o[0] = h;
@@ -2975,6 +3018,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
     }
     REC_TRACE(k, 4);
     t_prev = t;
+    yrow += ysl; arow += ysl; grow += gsl;
     REC_TRACE(k, 5);
   }
   if (IOW && w >= CW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the IO waves' DMAs (ahead of T) land
@@ -2983,7 +3027,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
     if constexpr (IO_OUT) {
       if (w >= CW) io_out(T - 1);  // outl of the last step: written before the loop's last barrier
     } else {
-      out_store(t_prev);
+      out_store(yrow - ysl, grow - gsl, arow - ysl);
     }
   }
   if ((fcopy || p.ysc1) && !bad) {  // the last step's copy / rows, then (workgroup 0) every producer's, then the epoch
@@ -4512,7 +4556,11 @@ int rnn_backward_weights(const RnnDesc &d, hipStream_t s, int T, int N, const fl
     // recurrences of this layer, which use the other flag words, are done)
     unsigned *fl = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + flags_offset(d, T, N));
     if (max_blocks > 0) g.tile_counter = reinterpret_cast<int *>(fl + 1008);
-    const bool x3 = use_x3((int)TN);  // K = frames: large (also for a 40-dim input: 0.8 ms/step over fp32)
+    // K = frames: large (also for a 40-dim input: 0.8 ms/step over fp32).
+    // A bf16 backward that wrote its dGates packed (bf16_direct) left no fp32
+    // rows: its packed operands are the only ones, however few the frames
+    // (under 128 frames the fp32 GEMMs below read rows nobody had written)
+    const bool x3 = use_x3((int)TN) || bf16_direct(d, 6);
     if (x3 && d.prec == kPrecBf16) {
       // bf16 weight GEMMs: the transposes packed along the frames as bf16
       const int KB = (int)((TN + 63) / 64);
