@@ -1453,12 +1453,6 @@ enum { kPrecX3 = 0, kPrecBf16 = 1, kPrecX3S = 2 };
 // + row r + 8 = hi B_hi + hi B_lo + lo B_hi + lo B_lo (all four terms: 2 MFMAs
 // per block instead of 3, and the lo x lo term the 3-MFMA form drops)
 
-// rows r + 8 of a 16 x 16 C fragment (lanes 32..63) added into rows r (lanes
-// 0..31); lanes 32..63 are left with garbage
-__device__ __forceinline__ float fold_rows8(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return x + __uint_as_float(r[1]);
-}
 // max over each aligned group of U (8, 16, 32) lanes, all lanes active
 __device__ __forceinline__ float group_maxU(float v, int U) {
   v = U > 8 ? group_max16(v) : group_max8(v);
@@ -1476,6 +1470,10 @@ constexpr int kFlagStride = 32;  // words
 constexpr int kXcdWord = 1016;
 constexpr int kResWord = 1017;  // v6 recurrence: workgroups resident so far (beside_recurrence)
 constexpr int kGateWord = 1018;  // blocks of its residency gate that left (rnn_resident_gate)
+// the named words: apart, clear of the tile and item counters (1008..1014)
+// and inside the words zeroed before every launch (v6 flag lines start at 1024)
+static_assert(kXcdWord > 1014 && kXcdWord < kResWord && kResWord < kGateWord && kGateWord < 1024,
+              "named flag words: distinct, above the counters, below 1024");
 __device__ __forceinline__ unsigned *flag6(const RecParams &p, int grp, int d, int g, int nwg) {
   return p.flags + 1024 + (((long)grp * p.dirs + d) * nwg + g) * kFlagStride;
 }
@@ -2467,6 +2465,9 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
   constexpr bool BF = PR == kPrecBf16;
   constexpr bool STK = PR == kPrecX3S;  // hi / lo stacked in one 16-row A operand (groups of <= 8 rows)
   constexpr int NP = BF ? 1 : 2;  // parts of an exchanged h: hi (+ lo)
+  // element rows: a stacked group has at most 8, and the folded K partials of
+  // a wave are 8 rows (no thread, no LDS row for the rows that cannot be live)
+  constexpr int ER = STK ? 8 : 16;
   static_assert(16 * U <= NTH, "one (row, unit) element per thread");
   static_assert(!IOW || (16 * U == CW * 64 && NW <= 4 && NP * 16 * U / 8 <= 64),
                 "IO waves: the elements fill the compute waves, one publishing wave");
@@ -2495,6 +2496,8 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
   // publish waited for every store of the step still in flight)
   constexpr int RPR = (U % 16 == 0 && NW <= 4 && 4 * U > RP) ? 4 * U : RP;  // red floats per (wave, row)
   constexpr int kStgOff = (NWV * 16 * RPR + 3 + 3) / 4 * 4;
+  // (stacked: [CW][8][U] float4, the first half of these floats)
+  static_assert(!STK || (U % 16 == 0 && NW <= 4), "stacked: float4 K partials");
   AT *stg = reinterpret_cast<AT *>(smem + kStgOff);
   // IO waves: the G rows of step k in slot k & 7, [8][NW][16 U] floats,
   // filled by LDS-DMA p.gla (3 or 7) steps ahead
@@ -2559,7 +2562,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
     }
   }
   // ---- per-element state: thread tid <-> (row n0 + en, unit u0 + eu) ----
-  const bool has_e = tid < 16 * U;
+  const bool has_e = tid < ER * U;
   const int en = tid / U, eu = tid - en * U;
   const int n = n0 + en;
   const bool live = has_e && n < nend;
@@ -2743,6 +2746,8 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
   const long gimg = (long)grp * XG;
   const bool pub = tid < NP * 16 * CH && n0 + sn < nend;  // a publishing thread: 16 B of h
   const long po = gimg + ((((long)d * KB + kb0) * NP + sp) * 16 + sn) * 32 + koff;
+  // stacked fold: the two rows of a tile this lane keeps (row, row + 1)
+  const int frow = (fq & 1) * 4 + (fq >> 1) * 2;
   int t_prev = -1;
   for (int k = 0; k < T && !bad; k++) {
     const int t = d == 0 ? k : T - 1 - k, tp = d == 0 ? t - 1 : t + 1;
@@ -2875,13 +2880,33 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
     // row, unit) [NWV][16][U][4], and a cell thread sums NWV float4 reads
     // (4x fewer LDS instructions than one float per gate)
     constexpr bool RED4 = U % 16 == 0 && NW <= 4;
-    if constexpr (STK) {  // rows 8..15 hold the lo parts' products: fold them into rows 0..7
+    if constexpr (STK) {
+      // Rows 8..15 of a tile (lanes 32..63) hold the lo parts' products of rows
+      // 0..7: row r + row r + 8, hi first.  v_permlane32_swap of register i
+      // against register i + 2 (not against itself): one swap serves two rows,
+      // every lane ends with two live sums: lanes 0..31 rows fq * 4 + {0, 1},
+      // lanes 32..63 rows (fq - 2) * 4 + {2, 3}  (= frow, frow + 1).  Half the
+      // swaps, no garbage lanes, and a wave's partials are 8 rows of float4
+      constexpr int SU = U / 16;
+      float sm2[CT][2];
 #pragma unroll
       for (int ct = 0; ct < CT; ct++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) acc[ct][i] = fold_rows8(acc[ct][i]);
-    }
-    if constexpr (RED4) {
+        for (int j = 0; j < 2; j++) {
+          const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[ct][j]), __float_as_uint(acc[ct][j + 2]),
+                                                          false, false);
+          sm2[ct][j] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+        }
+#pragma unroll
+      for (int su = 0; su < SU; su++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          floatx4 v4 = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int q = 0; q < NW; q++) v4[q] = sm2[q * SU + su][j];
+          st4(red + (((long)(w * ER + frow + j) * U + su * 16 + fr) << 2), v4);
+        }
+    } else if constexpr (RED4) {
       constexpr int SU = U / 16;
       if (!IOW || w < CW) {
 #pragma unroll
@@ -2911,7 +2936,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
       if constexpr (RED4) {
         floatx4 sm = *reinterpret_cast<const floatx4 *>(red + (((long)en * U + eu) << 2));  // fixed order
 #pragma unroll
-        for (int v = 1; v < CW; v++) sm += *reinterpret_cast<const floatx4 *>(red + (((long)(v * 16 + en) * U + eu) << 2));
+        for (int v = 1; v < CW; v++) sm += *reinterpret_cast<const floatx4 *>(red + (((long)(v * ER + en) * U + eu) << 2));
         if constexpr (IOW) {  // this step's G row, put there by the IO waves
 #pragma unroll
           for (int q = 0; q < NW; q++) gin[q] = ginl[((k & 7) * NW + q) * 16 * U + tid];
