@@ -198,6 +198,31 @@ int kctc_nnet_set_precision(kctcNnet_t nnet, int precision);
  * counters accumulate in the delta copy.  0 (default) = plain SGD. */
 int kctc_nnet_set_momentum(kctcNnet_t nnet, float momentum);
 
+/* DropoutComponent (src/nnet2/nnet-component.cc:3508-3611; the recipe's
+ * steps/ctc/train.sh --dropout-proportion).  The mask is not stored: forward
+ * and backward compute it from Philox4x32-10 keyed by (seed, component index)
+ * and a per-component draw counter that every Propagate increments (the
+ * scheme: csrc/dropout.h, restated in numpy by the Python package's
+ * dropout_mask).  kctc_nnet_create seeds the DropoutComponents with its
+ * `seed`; a network read from a file starts at seed 0.  Dropout draws nothing
+ * from the rand() stream of kctc_nnet_srand.  Data-parallel ranks created
+ * with the same seed share their masks; give each rank a seed of its own for
+ * independent ones.
+ *   kctc_nnet_set_dropout_seed  <- the role of CuRand's seed: component c gets
+ *                                  stream (seed, c), draw counters restart at 0
+ *   kctc_nnet_remove_dropout    <- Nnet::RemoveDropout (nnet-nnet.cc:507-524;
+ *                                  nnet-am-copy --remove-dropout=true): deletes
+ *                                  the DropoutComponents of the live network,
+ *                                  *removed (nullable) = how many; the other
+ *                                  components and their parameters stay, and
+ *                                  the trainer chains RNN -> ClipGradient -> RNN
+ *                                  again
+ *   kctc_nnet_set_dropout_scale <- Nnet::SetDropoutScale (nnet-nnet.cc:526-538)
+ * None of them may be called with minibatches in flight. */
+int kctc_nnet_set_dropout_seed(kctcNnet_t nnet, unsigned long long seed);
+int kctc_nnet_remove_dropout(kctcNnet_t nnet, int *removed);
+int kctc_nnet_set_dropout_scale(kctcNnet_t nnet, float scale);
+
 /* TrainNnetSimple (src/ctc/ctc-nnet-train.cc:185-284) over a background egs
  * reader (include/kaldi_ctc_egs.h, opened with the trainer's minibatch_size /
  * max_allow_frames): every minibatch is formatted on the GPU and trained with

@@ -2,7 +2,15 @@
  * kaldi_nnet2_component.h -- C ABI of the nnet2 Component plug-in point
  * (src/nnet2/nnet-component.h:157-348) for the components of the CTC path:
  * SpliceComponent, CuDNNRecurrentComponent (HIP recurrences, csrc/rnn.hip),
- * ClipGradientComponent, AffineComponent and SoftmaxComponent.
+ * ClipGradientComponent, AffineComponent, SoftmaxComponent and
+ * DropoutComponent (regenerated Philox mask, csrc/dropout.hip).
+ *
+ * A DropoutComponent handle made by kctc_component_init(line, seed, ...) draws
+ * from stream 0 of `seed`; every Propagate uses the next draw, and its
+ * Backprop applies the mask of the handle's last Propagate (it needs neither
+ * in_value nor out_value, and in_deriv may alias out_deriv).  A copy
+ * (kctc_component_copy, kctc_nnet_get_component) carries seed, stream and draw
+ * counter, so it reproduces the original's last mask.
  *
  * Each entry names the reference member it replaces:
  *   kctc_component_init        <- Component::NewComponentOfType + InitFromString

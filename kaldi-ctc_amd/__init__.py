@@ -297,12 +297,18 @@ def _tcheck(st, where):
 
 def recipe_config(num_rnn=5, input_dim=40, hidden=512, num_targets=41, rnn_mode=2, bidirectional=True,
                   learning_rate=5e-4, max_seq_length=2000, clipping_threshold=30.0, param_stddev=0.02,
-                  bias_stddev=0.2, num_layers=1, norm_based_clipping=True, splice_context=(0,)):
+                  bias_stddev=0.2, num_layers=1, norm_based_clipping=True, splice_context=(0,),
+                  dropout_proportion=0.0):
     """Component config lines of the CTC recipe, as written by
     egs/wsj/s5/steps/ctc/nnet2/components.py:73-102 (AddRnnLayer ->
     CuDNNRecurrentComponent + ClipGradientComponent) and an output
     AffineComponent; Splice first (make_configs.py: context 0; any sorted
-    offsets containing <= 0 and >= 0 values splice frames)."""
+    offsets containing <= 0 and >= 0 values splice frames).
+    dropout_proportion > 0 (train.sh --dropout-proportion) puts the generator's
+    "DropoutComponent dim=<out> dropout-proportion=<P>" between every RNN and
+    its ClipGradientComponent (components.py:67-71,94-95)."""
+    if not 0.0 <= dropout_proportion < 1.0:
+        raise ValueError("dropout_proportion must be in [0, 1)")
     ctx = [int(c) for c in splice_context]
     lines = [f"SpliceComponent input-dim={input_dim} context={':'.join(map(str, ctx))}"]
     dim = input_dim * len(ctx)
@@ -312,11 +318,61 @@ def recipe_config(num_rnn=5, input_dim=40, hidden=512, num_targets=41, rnn_mode=
                      f"bidirectional={'true' if bidirectional else 'false'} max-seq-length={max_seq_length} "
                      f"learning-rate={learning_rate} rnn-mode={rnn_mode} num-layers={num_layers} "
                      f"param-stddev={param_stddev} bias-stddev={bias_stddev}")
+        if dropout_proportion > 0:
+            lines.append(f"DropoutComponent dim={out} dropout-proportion={dropout_proportion}")
         lines.append(f"ClipGradientComponent dim={out} clipping-threshold={clipping_threshold} "
                      f"norm-based-clipping={'true' if norm_based_clipping else 'false'}")
         dim = out
     lines.append(f"AffineComponent input-dim={dim} output-dim={num_targets} learning-rate={learning_rate}")
     return "\n".join(lines) + "\n"
+
+
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Random123): counter = four uint32 arrays (or ints) of one
+    shape, key = two uint32 ints -> four uint32 arrays of that shape."""
+    c = [np.asarray(x, dtype=np.uint64) & np.uint64(0xffffffff) for x in counter]
+    k0, k1 = int(key[0]) & 0xffffffff, int(key[1]) & 0xffffffff
+    mask, s32 = np.uint64(0xffffffff), np.uint64(32)
+    for _ in range(10):
+        p0 = np.uint64(_PHILOX_M0) * c[0]
+        p1 = np.uint64(_PHILOX_M1) * c[2]
+        c = [(p1 >> s32) ^ c[1] ^ np.uint64(k0), p1 & mask, (p0 >> s32) ^ c[3] ^ np.uint64(k1), p0 & mask]
+        k0 = (k0 + _PHILOX_W0) & 0xffffffff
+        k1 = (k1 + _PHILOX_W1) & 0xffffffff
+    return [x.astype(np.uint32) for x in c]
+
+
+def dropout_mask(seed, stream, draw, rows, dim, proportion, scale=0.0):
+    """The multiplier [rows, dim] float32 that a DropoutComponent with stream
+    identity (seed, stream) applies in its Propagate number `draw` (0-based)
+    and in the Backprop after it -- the documented contract of csrc/dropout.h,
+    restated in numpy:
+
+    element i = r * dim + c uses word i % 4 of the Philox4x32-10 block with
+    counter (v & 0xffffffff, v >> 32, draw, stream), v = i // 4, and key
+    (seed & 0xffffffff, seed >> 32); it is kept iff word >= thr with
+    thr = floor(float32(proportion) * 2**32) computed in double; the
+    multiplier is low = float32(scale) where dropped and
+    high = float32((1 - dp * low) / (1 - dp)) (in double, from the float32 dp
+    and low) where kept.  In a network, component c has stream = c and the seed
+    of Nnet(seed=...) / Nnet.set_dropout_seed; a standalone Component(line,
+    seed) has stream 0."""
+    dp, low = np.float32(proportion), np.float32(scale)
+    if not 0.0 <= dp < 1.0 or not 0.0 <= low <= 1.0:
+        raise ValueError("proportion must be in [0, 1) and scale in [0, 1]")
+    n = int(rows) * int(dim)
+    thr = np.uint32(int(np.floor(float(dp) * 4294967296.0)))
+    high = np.float32((1.0 - float(dp) * float(low)) / (1.0 - float(dp)))
+    v = np.arange((n + 3) // 4, dtype=np.uint64)
+    seed = int(seed) & 0xffffffffffffffff
+    words = philox4x32_10((v & np.uint64(0xffffffff), v >> np.uint64(32), int(draw) & 0xffffffff,
+                           int(stream) & 0xffffffff), (seed & 0xffffffff, seed >> 32))
+    w = np.stack(words, axis=1).reshape(-1)[:n]
+    return np.where(w >= thr, high, low).astype(np.float32).reshape(int(rows), int(dim))
 
 
 class Nnet:
@@ -554,6 +610,22 @@ class Nnet:
 
     def set_momentum(self, m):
         _tcheck(lib().kctc_nnet_set_momentum(self.h, float(m)), "set_momentum")
+
+    def set_dropout_seed(self, seed):
+        """DropoutComponent c draws from stream (seed, c) of dropout_mask, from
+        draw 0 again (kctc_nnet_set_dropout_seed)."""
+        _tcheck(lib().kctc_nnet_set_dropout_seed(self.h, int(seed) & 0xffffffffffffffff), "set_dropout_seed")
+
+    def remove_dropout(self):
+        """nnet-am-copy --remove-dropout=true (Nnet::RemoveDropout) on the live
+        network -> the number of components removed."""
+        r = ctypes.c_int()
+        _tcheck(lib().kctc_nnet_remove_dropout(self.h, ctypes.byref(r)), "remove_dropout")
+        return r.value
+
+    def set_dropout_scale(self, scale):
+        """Nnet::SetDropoutScale: the dropped elements' multiplier of every DropoutComponent."""
+        _tcheck(lib().kctc_nnet_set_dropout_scale(self.h, float(scale)), "set_dropout_scale")
 
     def train_simple(self, reader, max_minibatches=0):
         """TrainNnetSimple over an EgsReader -> dict(num_egs, tot_weight, tot_objf, tot_accuracy)."""

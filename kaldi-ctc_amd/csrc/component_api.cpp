@@ -183,6 +183,8 @@ int kctc_component_init(kctcComponent_t *out, const char *line, unsigned long lo
     h->activate();
     kctc::nnet2::Rng rng(seed);
     h->c->InitFromString(rest, rng);
+    // a standalone DropoutComponent draws from stream 0 of `seed`
+    if (auto *d = dynamic_cast<kctc::nnet2::DropoutComponent *>(h->c.get())) d->SetSeed(seed, 0);
     h->sync();
     *out = h.release();
   });

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "ctc.h"
 #include "decodable.h"
+#include "dropout.h"
 #include "elementwise.h"
 #include "gemm.h"
 #include "prof.h"
@@ -279,6 +280,7 @@ Component *Component::NewComponentOfType(const std::string &type) {
   if (type == "ClipGradientComponent") return new ClipGradientComponent;
   if (type == "AffineComponent") return new AffineComponent;
   if (type == "SoftmaxComponent") return new SoftmaxComponent;
+  if (type == "DropoutComponent") return new DropoutComponent;
   return nullptr;
 }
 
@@ -1033,6 +1035,96 @@ void ClipGradientComponent::Read(std::istream &is, bool binary) {
   KCTC_HIP_CHECK(hipMemcpy(dev_, &h, sizeof(h), hipMemcpyHostToDevice));
 }
 // ---------------------------------------------------------------------------
+// DropoutComponent (nnet-component.cc:3508-3611)
+// ---------------------------------------------------------------------------
+// the reference asserts these in Propagate (:3570-3571)
+void DropoutComponent::Check(float proportion, float scale) {
+  if (!(proportion >= 0.f && proportion < 1.f))
+    throw std::invalid_argument("DropoutComponent: dropout-proportion must be in [0, 1)");
+  if (!(scale >= 0.f && scale <= 1.f)) throw std::invalid_argument("DropoutComponent: dropout-scale must be in [0, 1]");
+}
+void DropoutComponent::InitFromString(std::string args, Rng &) {  // :3516-3528
+  const std::string orig = args;
+  int dim = 0;
+  float proportion = 0.5f, scale = 0.0f;
+  const bool ok = ParseFromString("dim", &args, &dim);
+  ParseFromString("dropout-proportion", &args, &proportion);
+  ParseFromString("dropout-scale", &args, &scale);
+  if (!ok || !args.empty() || dim <= 0)
+    throw std::invalid_argument("Invalid initializer for layer of type DropoutComponent: \"" + orig + "\"");
+  Check(proportion, scale);
+  dim_ = dim;
+  dropout_proportion_ = proportion;
+  dropout_scale_ = scale;
+  draw_ = 0;
+}
+void DropoutComponent::SetDropoutScale(float scale) {
+  Check(dropout_proportion_, scale);
+  dropout_scale_ = scale;
+}
+std::string DropoutComponent::Info() const {
+  std::ostringstream os;
+  os << Type() << ", dim=" << dim_ << ", dropout-proportion=" << dropout_proportion_
+     << ", dropout-scale=" << dropout_scale_;
+  return os.str();
+}
+void DropoutComponent::Propagate(const ChunkInfo &, const ChunkInfo &, const CuMatrixBase &in,
+                                 CuMatrixBase *out) const {
+  if (in.NumCols() != dim_ || out->NumCols() != dim_ || in.NumRows() != out->NumRows())
+    throw std::invalid_argument("DropoutComponent::Propagate: bad shape");
+  ProfScope ps("dropout");
+  DropoutMask m;
+  m.seed = seed_; m.stream = stream_; m.draw = draw_++;
+  m.proportion = dropout_proportion_; m.scale = dropout_scale_;
+  dropout_forward(S(), in.Data(), out->Data(), in.NumRows() * (long)dim_, m);
+}
+void DropoutComponent::Backprop(const ChunkInfo &, const ChunkInfo &, const CuMatrixBase &, const CuMatrixBase &,
+                                const CuMatrixBase &out_deriv, Component *, CuMatrixBase *in_deriv) const {
+  if (!in_deriv) return;
+  if (out_deriv.NumCols() != dim_ || in_deriv->NumCols() != dim_ || in_deriv->NumRows() != out_deriv.NumRows())
+    throw std::invalid_argument("DropoutComponent::Backprop: bad shape");
+  if (draw_ == 0) throw std::logic_error("DropoutComponent::Backprop before any Propagate (no mask was drawn)");
+  ProfScope ps("dropout");
+  DropoutMask m;
+  m.seed = seed_; m.stream = stream_; m.draw = draw_ - 1;  // the last Propagate's
+  m.proportion = dropout_proportion_; m.scale = dropout_scale_;
+  dropout_backward(S(), out_deriv.Data(), in_deriv->Data(), out_deriv.NumRows() * (long)dim_, m);
+}
+Component *DropoutComponent::Copy() const {
+  auto *c = new DropoutComponent;
+  c->dim_ = dim_;
+  c->dropout_proportion_ = dropout_proportion_;
+  c->dropout_scale_ = dropout_scale_;
+  c->seed_ = seed_;
+  c->stream_ = stream_;
+  c->draw_ = draw_;
+  return c;
+}
+void DropoutComponent::Write(std::ostream &os, bool binary) const {  // :3540-3549
+  WriteToken(os, binary, "<DropoutComponent>");
+  WriteToken(os, binary, "<Dim>");
+  kio::WriteInt(os, binary, dim_);
+  WriteToken(os, binary, "<DropoutScale>");
+  kio::WriteFloat(os, binary, dropout_scale_);
+  WriteToken(os, binary, "<DropoutProportion>");
+  kio::WriteFloat(os, binary, dropout_proportion_);
+  WriteToken(os, binary, "</DropoutComponent>");
+}
+void DropoutComponent::Read(std::istream &is, bool binary) {  // :3530-3538
+  ExpectToken(is, binary, "<Dim>");
+  dim_ = kio::ReadInt(is, binary);
+  if (dim_ <= 0) throw std::runtime_error("DropoutComponent: bad <Dim>");
+  ExpectToken(is, binary, "<DropoutScale>");
+  dropout_scale_ = kio::ReadFloat(is, binary);
+  ExpectToken(is, binary, "<DropoutProportion>");
+  dropout_proportion_ = kio::ReadFloat(is, binary);
+  ExpectToken(is, binary, "</DropoutComponent>");
+  Check(dropout_proportion_, dropout_scale_);
+  seed_ = 0;
+  stream_ = 0;
+  draw_ = 0;
+}
+// ---------------------------------------------------------------------------
 // SoftmaxComponent (NonlinearComponent I/O, nnet-component.cc:383-426)
 // ---------------------------------------------------------------------------
 void SoftmaxComponent::InitFromString(std::string args, Rng &) {
@@ -1334,6 +1426,42 @@ void Nnet::SetMomentum(float m) {
   }
 }
 
+void Nnet::SetDropoutSeed(uint64_t seed) {
+  for (int c = 0; c < NumComponents(); c++)
+    if (auto *d = dynamic_cast<DropoutComponent *>(components_[c])) d->SetSeed(seed, (uint32_t)c);
+}
+
+int Nnet::RemoveDropout() {  // nnet-nnet.cc:507-524
+  std::vector<Component *> kept;
+  int removed = 0;
+  for (Component *c : components_) removed += dynamic_cast<DropoutComponent *>(c) ? 1 : 0;
+  if (removed == NumComponents()) throw std::invalid_argument("Nnet::RemoveDropout: nothing but dropout components");
+  removed = 0;
+  for (Component *c : components_) {
+    if (dynamic_cast<DropoutComponent *>(c)) {
+      delete c;
+      removed++;
+    } else {
+      kept.push_back(c);
+    }
+  }
+  components_ = kept;
+  // Check(): a DropoutComponent has equal input and output dimensions, so the
+  // neighbours still chain.  Packed operands and input bounds are set again
+  // by the next Propagate for the new neighbours.
+  for (Component *x : components_)
+    if (auto *r = dynamic_cast<CuDNNRecurrentComponent *>(x)) {
+      r->ClearPackedInput();
+      r->ClearInputBound();
+    }
+  return removed;
+}
+
+void Nnet::SetDropoutScale(float scale) {  // nnet-nnet.cc:526-538
+  for (Component *c : components_)
+    if (auto *d = dynamic_cast<DropoutComponent *>(c)) d->SetDropoutScale(scale);
+}
+
 void Nnet::SetLearningRate(float lr) {
   for (auto *c : components_)
     if (c->IsUpdatable()) static_cast<UpdatableComponent *>(c)->SetLearningRate(lr);
@@ -1372,11 +1500,19 @@ void Nnet::Read(std::istream &is, bool binary) {
                                ") and " + std::to_string(i + 1) + " (" + components_[i + 1]->Type() + ", input " +
                                std::to_string(components_[i + 1]->InputDim()) + ")");
   }
+  SetDropoutSeed(0);  // the file carries no stream identity
 }
 // ---------------------------------------------------------------------------
 // NnetCtcUpdater (src/ctc/ctc-nnet-update.cc:76-348)
 // ---------------------------------------------------------------------------
 NnetCtcUpdater::NnetCtcUpdater(Nnet *nnet, bool update) : nnet_(nnet), update_(update) {}
+
+void NnetCtcUpdater::ComponentsChanged() {
+  if (pending_) throw std::logic_error("the component list changed with queued minibatches (Finish them first)");
+  // indexed by component: rebuilt by the next minibatch (Output() is empty until then)
+  forward_data_.clear();
+  chunk_info_.clear();
+}
 
 static void set_minibatch(Nnet *nnet, int N) {  // Nnet::SetMiniBatch (nnet-nnet.cc:42-50)
   for (int c = 0; c < nnet->NumComponents(); c++) {
@@ -1603,6 +1739,7 @@ void NnetCtcUpdater::Propagate(int T, int N) {  // :136-169
       const void *rows = nullptr, *cols = nullptr;
       if (below && below->Desc().prec == r->Desc().prec) below->PackedOutput(&rows, &cols);
       r->SetPackedInput(rows, cols);
+      if (!below) r->ClearInputBound();  // e.g. above a DropoutComponent: |input| can exceed 1
       // Backprop computes its input derivative (streamed dx GEMM): W^T packed now
       r->SetPrepackDx(update_ && c > first);
       r->SetPrepackW(update_ && c >= first);

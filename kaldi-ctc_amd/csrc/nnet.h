@@ -11,7 +11,8 @@
 //   CuDNNRecurrentComponent             -> rnn.hip (cuDNN-shaped gfx950 kernels)
 //   ClipGradientComponent               -> elementwise.hip / clipgrad.hip
 //   AffineComponent                     -> gemm.hip
-//   Nnet                                component list, FirstUpdatableComponent
+//   DropoutComponent                    -> dropout.hip (regenerated Philox mask)
+//   Nnet                              component list, FirstUpdatableComponent
 //   NnetCtcUpdater                      ComputeForMinibatch: forward, warp-ctc ABI
 //                                       (ctc.hip), accuracy, backprop, SGD.
 // Differences from the reference, all semantics-preserving:
@@ -319,6 +320,10 @@ class CuDNNRecurrentComponent : public UpdatableComponent {
   }
   // the component below changed (Nnet::SetComponent): its packed output is gone
   void ClearPackedInput() const { SetPackedInput(nullptr, nullptr); }
+  // no RNN feeds this one through identity components: the bound on |input|
+  // that a PropagateChained once installed does not hold (a DropoutComponent's
+  // output reaches high > 1)
+  void ClearInputBound() const { input_bound_ = 0.f; }
 
  private:
   void Init(Rng &rng);
@@ -393,6 +398,53 @@ class ClipGradientComponent : public Component {
   ClipState *dev_ = nullptr;
   mutable DevBuf scratch_;
   ClipGradientComponent *shadow_ = nullptr;
+};
+
+// DropoutComponent (nnet-component.cc:3508-3611; the recipe's
+// --dropout-proportion puts one between every RNN and its ClipGradient).  The
+// mask is not stored: forward and backward compute it from a counter-based
+// generator (dropout.h) keyed by this component's stream identity
+// (seed_, stream_) and a draw counter.  Every Propagate, training or not, uses
+// the current draw and increments it (evaluation without dropout removes the
+// components, Nnet::RemoveDropout); Backprop applies the mask of the last
+// Propagate, so it needs neither the input nor the output (the reference's
+// out_deriv * out_value / in_value differs only at exact zeros of the input).
+// Seeding: Nnet::SetDropoutSeed gives component c the identity (seed, c) and
+// draw 0; a network read from a file starts at seed 0.  Data-parallel ranks
+// that create their networks with the same seed draw the same masks: ranks
+// share masks unless the caller seeds them differently.
+class DropoutComponent : public Component {
+ public:
+  std::string Type() const override { return "DropoutComponent"; }
+  int InputDim() const override { return dim_; }
+  int OutputDim() const override { return dim_; }
+  void InitFromString(std::string args, Rng &rng) override;
+  std::string Info() const override;
+  bool BackpropNeedsInput() const override { return false; }
+  bool BackpropNeedsOutput() const override { return false; }
+  void Propagate(const ChunkInfo &, const ChunkInfo &, const CuMatrixBase &in,
+                 CuMatrixBase *out) const override;
+  void Backprop(const ChunkInfo &, const ChunkInfo &, const CuMatrixBase &, const CuMatrixBase &,
+                const CuMatrixBase &out_deriv, Component *, CuMatrixBase *in_deriv) const override;
+  void Write(std::ostream &os, bool binary) const override;
+  void Read(std::istream &is, bool binary) override;
+  Component *Copy() const override;  // carries seed, stream and draw counter
+  void SetSeed(uint64_t seed, uint32_t stream) {  // the draw counter restarts
+    seed_ = seed;
+    stream_ = stream;
+    draw_ = 0;
+  }
+  void SetDropoutScale(float scale);  // nnet-component.h DropoutComponent::SetDropoutScale
+  float DropoutProportion() const { return dropout_proportion_; }
+  float DropoutScale() const { return dropout_scale_; }
+
+ private:
+  static void Check(float proportion, float scale);
+  int dim_ = 0;
+  float dropout_proportion_ = 0.5f, dropout_scale_ = 0.0f;
+  uint64_t seed_ = 0;
+  uint32_t stream_ = 0;
+  mutable uint32_t draw_ = 0;  // of the next Propagate
 };
 
 // SoftmaxComponent (nnet-component.cc:929-946): the output layer the recipe
@@ -480,6 +532,14 @@ class Nnet {
   void SetLearningRate(float lr);
   void SetMomentum(float m);
   float Momentum() const { return momentum_; }
+  // every DropoutComponent gets the stream identity (seed, its component
+  // index) and draw 0
+  void SetDropoutSeed(uint64_t seed);
+  // Nnet::RemoveDropout (nnet-nnet.cc:507-524): deletes the DropoutComponents,
+  // returns how many; the other components are untouched
+  int RemoveDropout();
+  // Nnet::SetDropoutScale (nnet-nnet.cc:526-538)
+  void SetDropoutScale(float scale);
   void Write(std::ostream &os, bool binary) const;
   void Read(std::istream &is, bool binary);
 
@@ -545,6 +605,9 @@ class NnetCtcUpdater {
   // test hook: the next minibatch's device error word starts as `word` (as if
   // a recurrence had timed out), so its updates are skipped and Finish throws
   void InjectStepError(unsigned word) { inject_err_ = word; }
+  // the network's component list changed (Nnet::RemoveDropout): forget what
+  // is kept per component index (no minibatch may be queued)
+  void ComponentsChanged();
 
  private:
   void SetupChunks(int T_max, int N);

@@ -355,6 +355,7 @@ int kctc_nnet_create(kctcNnet_t *out, const char *config, unsigned long long see
       n->activate();
       kctc::nnet2::Rng rng(seed);
       n->nnet.Init(config ? config : "", rng);
+      n->nnet.SetDropoutSeed(seed);  // a stream of its own: not the parameters' rng, not rand()
     } catch (...) {
       delete n;
       throw;
@@ -828,6 +829,41 @@ int kctc_nnet_set_momentum(kctcNnet_t n, float momentum) {
     KCTC_REQUIRE(n, "null nnet");
     n->activate();
     n->nnet.SetMomentum(momentum);
+  });
+}
+
+int kctc_nnet_set_dropout_seed(kctcNnet_t n, unsigned long long seed) {
+  return guarded([&] {
+    KCTC_REQUIRE(n, "null nnet");
+    KCTC_REQUIRE(n->trainer.Pending() == 0, "kctc_nnet_set_dropout_seed with minibatches in flight");
+    n->nnet.SetDropoutSeed(seed);
+  });
+}
+
+int kctc_nnet_set_dropout_scale(kctcNnet_t n, float scale) {
+  return guarded([&] {
+    KCTC_REQUIRE(n, "null nnet");
+    KCTC_REQUIRE(n->trainer.Pending() == 0, "kctc_nnet_set_dropout_scale with minibatches in flight");
+    n->nnet.SetDropoutScale(scale);
+  });
+}
+
+int kctc_nnet_remove_dropout(kctcNnet_t n, int *removed) {
+  return guarded([&] {
+    KCTC_REQUIRE(n, "null nnet");
+    KCTC_REQUIRE(n->trainer.Pending() == 0, "kctc_nnet_remove_dropout with minibatches in flight");
+    n->activate();
+    // the per-component buffers that go away may still be read by queued work
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+    if (n->side) KCTC_HIP_CHECK(hipStreamSynchronize(n->side));
+    if (n->stream2) KCTC_HIP_CHECK(hipStreamSynchronize(n->stream2));
+    const int r = n->nnet.RemoveDropout();
+    // momentum shadows and update deltas live in the components that stay, and
+    // the gradient exchange registers its buckets anew every step: what is
+    // indexed by component is the two updaters' forward data and chunk info
+    n->trainer.ComponentsChanged();
+    n->evaluator.ComponentsChanged();
+    if (removed) *removed = r;
   });
 }
 
