@@ -64,6 +64,10 @@ size_t rnn_workspace_bytes(const RnnDesc &d, int T, int N);
 void rnn_set_cu_budget(int cus, int comm);
 int rnn_usable_cus();
 int rnn_comm_cus();
+// test hook (test_hooks.h kctc_test_rec6_select): cfg = {U, nth, rg, gs,
+// variant} of the v6 recurrence that (d, N, fwd) runs (zeros: not a v6 shape)
+// and its kernel (nullptr then); nothing is launched
+const void *rnn_rec6_select(const RnnDesc &d, int N, bool fwd, int cfg[5]);
 
 // Residency gate of the gradient exchange.  Every workgroup
 // of a v6 backward recurrence adds 1 to a per-device 64-bit registration

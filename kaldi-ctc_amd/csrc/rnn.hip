@@ -38,7 +38,8 @@
 // row 1).  Every spin is bounded (3 s); a timeout sets the device error word,
 // every workgroup drains out and the train step fails loudly.
 // v4 (fp32 MFMA, XCD-slot all-gather) and v3 remain for the shapes v6 does
-// not compile (RELU / TANH, other H, N > 64).
+// not compile (RELU / TANH, other H, N > 64).  This file is the host side; the
+// kernels: rec6_fwd.hip, rec6_bwd.hip, rec_generic.hip (v3 / v4), rec_common.h.
 //
 // Semantics follow cuDNN v5 as used by CuDNNRecurrentComponent: hx = cx = 0,
 // dhy = dcy = 0 (SetBufferZero, nnet-cudnn-component.cc:494-506), all N
@@ -58,9 +59,8 @@
 #include "elementwise.h"
 #include "gemm.h"
 #include "prof.h"
+#include "rec_common.h"
 #include "rnn.h"
-
-#include <functional>
 
 namespace kctc {
 
@@ -103,7 +103,7 @@ RnnReserveLayout rnn_reserve_layout(const RnnDesc &d, int T, int N) {
   r.out = p;  p += (d.layers > 1) ? al64(TN * dirs * H) : 0;
   r.dout = p; p += (d.layers > 1) ? al64(TN * dirs * H) : 0;
   r.kbt64 = (TN + 63) / 64 * 64;
-  const bool pkd = d.prec == 1 /* kPrecBf16 */ && d.layers == 1 && d.pk;  // bf16 halves: 2 per float
+  const bool pkd = d.prec == kPrecBf16 && d.layers == 1 && d.pk;  // bf16 halves: 2 per float
   const long G4 = nw * H, kbg64 = (G4 + 63) / 64 * 64;
   r.pkxr = p; p += pkd ? al64((dirs * TN * kbg64 + 1) / 2) : 0;
   r.pkxt = p; p += pkd ? al64((dirs * G4 * r.kbt64 + 1) / 2) : 0;
@@ -214,15 +214,14 @@ static P *pk(void *ws, const RnnDesc &d, int T, int N, size_t off) {
 }
 // The RNN GEMMs run on the packed split-fp16 matrix-core path (gemm_x3p.hip)
 // unless the contraction is too short to pay for packing.
-static bool use_x3(int K, int min_k = 128) {
-  return K >= min_k;
-}
+static bool use_x3(int K, int min_k = 128) { return K >= min_k; }
 // |x| <= 1: an LSTM / GRU / TANH layer output
 static bool bounded_out(const RnnDesc &d) { return d.mode != kRelu; }
 
-namespace {
-int env_int(const char *name, int dflt);
-}  // namespace
+static int env_int(const char *name, int dflt) {
+  const char *v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 
 // bf16 recurrences write their dGates straight into the packed bf16 GEMM
 // operands (RecParams::dxr / dxt / et) -- v6 only (a v6 backward runs for
@@ -230,7 +229,7 @@ int env_int(const char *name, int dflt);
 // (one-layer descriptors -- the recipe's components; a stacked descriptor's
 // weight gradients measured wrong with it, so those keep the pack path)
 static bool bf16_direct(const RnnDesc &d, int ver) {
-  return d.prec == 1 /* kPrecBf16 */ && ver == 6 && (d.nw() * d.H) % 64 == 0 && d.layers == 1 && d.pk;
+  return d.prec == kPrecBf16 && ver == 6 && (d.nw() * d.H) % 64 == 0 && d.layers == 1 && d.pk;
 }
 // ... and, one-layer bidirectional, the forward writes its output packed
 // (RecParams::yr / yc) and the backward E^T shifted (eshift); H % 32 == 0 so
@@ -239,2977 +238,14 @@ static bool bf16_io(const RnnDesc &d) {
   return bf16_direct(d, 6) && d.layers == 1 && d.dirs == 2 && d.H % 32 == 0 && (2 * d.H) % 64 == 0 && d.pkio;
 }
 
-
-
 namespace {
 
-constexpr int NT = 256;
-constexpr unsigned kSent = 0xFFFFFFFFu;
-constexpr int kSpinLimit = 1 << 21;
-constexpr int kMaxRT = 4;  // N <= 64 (four 16-row MFMA tiles)
-constexpr int kMaxCT = 4;  // <= 64 gate columns per workgroup
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool ready4(u32x4 v) {
-  return (v[0] != kSent) & (v[1] != kSent) & (v[2] != kSent) & (v[3] != kSent);
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void *base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
-}
-
-__device__ __forceinline__ u32x4 ld_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 16 /* sc1 */);
-}
-
-// Re-poll one 16-byte fragment until it holds no sentinel (bounded spin).
-__device__ __forceinline__ u32x4 settle(__amdgpu_buffer_rsrc_t r, unsigned off, u32x4 v,
-                                        unsigned *err, int &bad) {
-  int spins = 0;
-  while (!bad && !ready4(v)) {
-    if (++spins > kSpinLimit) { bad = 1; break; }
-    if ((spins & 255) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-      bad = 1;
-      break;
-    }
-    __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-    v = ld_sc1(r, off);
-  }
-  return v;
-}
-
-__device__ __forceinline__ void publish(float *p, float v) {
-  unsigned u = __float_as_uint(v);
-  if (u == kSent) u = 0x7FC00000u;  // never publish the sentinel bit pattern
-  __hip_atomic_store(reinterpret_cast<unsigned *>(p), u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-
-struct RecParams {
-  int T, N, H, dirs, U, nwg, ncol, Npad;
-  int rg;           // v6: row groups (independent recurrences) of gs sequences
-  int gs;           // v6: sequences per row group (16, or 8: two groups of a 16-row batch run side by side)
-  const float *w;   // params base of this stacked layer's pseudo-layer 0
-  long pl_stride;   // floats between the two directions' blocks
-  long r_off;       // R within a pseudo-layer block
-  long bR_off;      // bR within a pseudo-layer block
-  float *G;         // [T*N][dirs*nW*H] pre-activations -> activations
-  float *y;         // [T*N][dirs*H] output / h exchange (sentinel pre-filled)
-  float *aux;       // LSTM: c ; GRU: R_n h + b_Rn   [T*N][dirs*H]
-  const float *dy;  // backward: [T*N][dirs*H]
-  float *E;         // backward: dGates (recurrent part) exchange [T*N][dirs*nW*H]
-  float *DX;        // backward GRU: dGates (input part); == E otherwise
-  float *bias;      // backward: bias partial sums [dirs][2][nW*H]
-  unsigned *flags;  // flag protocol: [dirs][nwg] step epochs, zeroed before launch
-  unsigned *err;
-  int sync;         // kSyncData / kSyncFlag
-  unsigned long long *trace;  // optional: [kTraceSteps][grid][8] s_memrealtime stamps
-  int allow_local;  // v4: hand off through the shared L2 when placement allows it
-  int xpd;          // v4: XCD slots per direction (nwg = 32 * xpd workgroups)
-  int ring;         // v6: hand-off images reused every `ring` steps (0: one image per step; forward: ring after the T step images)
-  int fcopy;        // v6 forward, XCD-pinned: h images also written through (sc1) per step for a streamed projection
-  float *xch;       // v4: per-step exchange images [T][dirs][KG][Npad][16] (workspace)
-  int poll_sleep;   // v6: s_sleep between flag polls
-  int gla;          // v6 forward IO waves: steps ahead the G rows are fetched (3 or 7; 8 LDS slots)
-  int e_sc1;        // v6 backward: dGates rows written through (sc1) for a streaming consumer
-  int ysc1;         // v6 forward: y rows written through (sc1) and the aggregated epochs published
-                    // for the next component's projection streamed off them (launch_chain_rows)
-  int bfpart;       // v6 backward, bf16 mode: partial dh exchanged as bf16
-  unsigned *cmax;   // v6 backward: column max |DX| [dirs * nW * H] (GRU: then |E|), as float bits
-  unsigned *reg;    // v6 backward: per-device registration word (+1 per workgroup at start)
-  // v6 backward, bf16 (RnnReserveLayout::pk): dGates written straight into the
-  // packed bf16 operands of the GEMMs after the recurrence, instead of fp32
-  // rows that pack kernels re-read: dxr = DX rows [dir][T*N][nW*H] (A of the
-  // dx GEMM), dxt = DX^T [dir][nW*H][kbt64] (A of dW), et = E^T (A of dR; ==
-  // dxt for an LSTM), frames along the packed rows (kbt64 >= T*N, zero tail)
-  __bf16 *dxr, *dxt, *et;
-  long kbt64;
-  // bf16 one-layer bidirectional (bf16_io): the forward writes its output h as
-  // packed bf16 too -- yr = rows [T*N][dirs*H] (A of the next component's
-  // input projection), yc = columns [dirs*H][kbt64] (B of this component's dR
-  // and of the next component's dW) -- and the backward then writes E^T
-  // shifted by one step (eshift: direction 0 frame f at f - N, direction 1 at
-  // f + N), so that dR pairs it with the unshifted yc
-  __bf16 *yr, *yc;
-  int eshift;
-  // v6 backward, fp32 partials, ring of 2: self-tagged hand-off (see
-  // rnn_bwd_rec6): the consumers poll the partial-dh words themselves instead
-  // of the producers' epoch flags; taken by the slots probe6 finds XCD-local
-  // (v6 forward, split-fp16 without IO waves: the same for the h hi / lo
-  // halves, each carrying the tag in its LSB)
-  int dtag;
-};
-
-// Phase stamps of the first kTraceSteps steps ([steps][grid][16]; thread 0 of every workgroup;
-// 100 MHz constant clock), only when the host passes a trace buffer
-// (KCTC_REC_TRACE): 0 step start, 1 flags seen, 2 operand loads landed,
-// 3 MFMA + K reduction done, 4 published (+ flag), 5 step end.
-// v6 backward: slots 16 + w flags seen by wave w, 24 + w its hand-off loads landed.
-constexpr int kTraceSteps = 256, kTraceStride = 32;
-// (the cursor trc_ / trg_ of REC_TRACE_INIT lives in VGPRs: the stamps cost
-// the step loop no scalar registers)
-#define REC_TRACE_INIT                                                                    \
-  unsigned long long *trc_ = p.trace ? p.trace + (long)blockIdx.x * kTraceStride : nullptr; \
-  long trg_ = (long)gridDim.x * kTraceStride;                                             \
-  asm volatile("" : "+v"(trc_), "+v"(trg_))
-#define REC_TRACE(kk, ph)                                                                 \
-  do {                                                                                    \
-    if (trc_ && threadIdx.x == 0 && (kk) < kTraceSteps) {                                 \
-      unsigned long long *tr_ = trc_ + (long)(kk) * trg_;                                 \
-      tr_[(ph)] = __builtin_amdgcn_s_memrealtime();                                       \
-      if ((ph) == 2 || (ph) == 3) tr_[12 + (ph)] = __builtin_amdgcn_s_memtime();          \
-    }                                                                                     \
-  } while (0)
-// per-wave stamps (lane 0 of every wave): slot 6 + w loads landed, 10 + w MFMA done;
-// slots 14/15: shader-clock counter (s_memtime) at phases 2/3 (clock estimate)
-#define REC_TRACE_W(kk, ph)                                                               \
-  do {                                                                                    \
-    if (trc_ && (threadIdx.x & 63) == 0 && (kk) < kTraceSteps)                            \
-      trc_[(long)(kk) * trg_ + (ph) + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-
-// Hand-off protocols (selected per launch; both placement-independent):
-//  kSyncData: the payload is the flag (sentinel-filled buffer, sc1 4-B stores,
-//             sc1 16-B loads re-polled until no sentinel is left).
-//  kSyncFlag: payload sc1 stores -> every storing wave s_waitcnt vmcnt(0) ->
-//             workgroup barrier -> ONE lane stores the step epoch (sc1) into
-//             the workgroup's flag word; consumers: wave 0 polls the nwg flag
-//             words of its direction with one sc1 load per lane, barrier, then
-//             every wave loads the payload with sc1 loads (MI355X_MICROARCH.md
-//             "Valid forms", row 1).  Polling traffic: 4 B per producer, not
-//             the whole payload.
-enum { kSyncData = 0, kSyncFlag = 1 };
-
-__device__ __forceinline__ void wait_flags(const unsigned *flags, int nwg, unsigned epoch,
-                                           unsigned *err, int &bad, int *bad_lds) {
-  if (threadIdx.x < 64) {
-    int spins = 0;
-    while (true) {
-      bool ok = true;
-      for (int i = threadIdx.x; i < nwg; i += 64)
-        ok &= __hip_atomic_load(flags + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= epoch;
-      if (__all(ok)) break;
-      if (++spins > kSpinLimit ||
-          ((spins & 255) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-        bad = 1;
-        if (threadIdx.x == 0) *bad_lds = 1;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-  }
-  __syncthreads();
-  if (*bad_lds) bad = 1;
-}
-
-__device__ __forceinline__ void signal_flag(unsigned *flag, unsigned epoch) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its sc1 stores
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// A-operand fragments of one step: rows n (RT 16-row tiles) x this wave's
-// k-groups {w, w+4, ...}, CH k-groups per pass, straight from the exchange
-// buffer into registers with sc1 16-B loads.  Returns false on timeout.
-template <int RT, int CH>
-__device__ __forceinline__ void load_frags(u32x4 (&af)[RT][CH], __amdgpu_buffer_rsrc_t rs, long ld,
-                                           long col0, int c0, int KG, int N, int sync, unsigned *err,
-                                           int &bad) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fr = lane & 15, fq = lane >> 4;
-#pragma unroll
-  for (int i = 0; i < CH; i++) {
-    const int kg = w + 4 * (c0 + i);
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) {
-      const int n = rt * 16 + fr;
-      af[rt][i] = u32x4{0u, 0u, 0u, 0u};
-      if (kg < KG && n < N) af[rt][i] = ld_sc1(rs, (unsigned)(((long)n * ld + col0 + kg * 16 + fq * 4) * 4));
-    }
-  }
-  if (sync == kSyncData) {
-#pragma unroll
-    for (int i = 0; i < CH; i++) {
-      const int kg = w + 4 * (c0 + i);
-#pragma unroll
-      for (int rt = 0; rt < RT; rt++) {
-        const int n = rt * 16 + fr;
-        if (kg < KG && n < N)
-          af[rt][i] = settle(rs, (unsigned)(((long)n * ld + col0 + kg * 16 + fq * 4) * 4), af[rt][i], err, bad);
-      }
-    }
-  }
-}
-
-// 16-byte write-through (sc1) publish of 4 consecutive units: every A-operand
-// fragment a consumer loads (4 consecutive k) is exactly one such store, so a
-// fragment is either all-sentinel or all-final (no tearing to re-poll).
-__device__ __forceinline__ floatx4 canon(floatx4 v) {
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-    if (__float_as_uint(v[i]) == kSent) v[i] = __uint_as_float(0x7FC00000u);
-  return v;
-}
-__device__ __forceinline__ void publish4(__amdgpu_buffer_rsrc_t r, unsigned off, floatx4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, canon(v)), r, (int)off, 0, 16);
-}
-__device__ __forceinline__ floatx4 ld4(const float *p) { return *reinterpret_cast<const floatx4 *>(p); }
-__device__ __forceinline__ void st4(float *p, floatx4 v) { *reinterpret_cast<floatx4 *>(p) = v; }
-__device__ __forceinline__ floatx4 sigm4(floatx4 x) {
-  floatx4 r;
-#pragma unroll
-  for (int i = 0; i < 4; i++) r[i] = sigm(x[i]);
-  return r;
-}
-__device__ __forceinline__ floatx4 tanh4(floatx4 x) {
-  floatx4 r;
-#pragma unroll
-  for (int i = 0; i < 4; i++) r[i] = tanhf(x[i]);
-  return r;
-}
-
-// Poll every not-yet-valid fragment of this lane in batches: all re-loads of
-// a round are in flight together, so a round costs one memory round trip.
-template <int RT, int CH>
-__device__ __forceinline__ void settle_all(u32x4 (&af)[RT][CH], __amdgpu_buffer_rsrc_t rs, long ld,
-                                           long col0, int c0, int KG, int N, unsigned *err, int &bad) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fr = lane & 15, fq = lane >> 4;
-  for (int round = 0; !bad; round++) {
-    int pending = 0;
-#pragma unroll
-    for (int i = 0; i < CH; i++) {
-      const int kg = w + 4 * (c0 + i);
-#pragma unroll
-      for (int rt = 0; rt < RT; rt++) {
-        const int n = rt * 16 + fr;
-        if (kg < KG && n < N && !ready4(af[rt][i])) {
-          af[rt][i] = ld_sc1(rs, (unsigned)(((long)n * ld + col0 + kg * 16 + fq * 4) * 4));
-          pending++;
-        }
-      }
-    }
-    if (!pending) break;
-    if (round > kSpinLimit ||
-        ((round & 255) == 255 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-      bad = 1;
-      break;
-    }
-    asm volatile("" ::: "memory");
-  }
-}
-
-// ---------------------------------------------------------------------------
-// forward recurrence
-// ---------------------------------------------------------------------------
-template <int MODE, int RT>
-__global__ __launch_bounds__(NT, 1) void rnn_fwd_rec(RecParams p) {
-  REC_TRACE_INIT;
-  constexpr int NW = MODE == kLstm ? 4 : MODE == kGru ? 3 : 1;
-  constexpr int CH = 32 / RT;  // k-groups per wave per pass (<= 32 A-fragment registers x4)
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds;
-  const int H = p.H, U = p.U, N = p.N, T = p.T, ncol = p.ncol;
-  const int LDR = H + 4;
-  const int d = blockIdx.x / p.nwg, g = blockIdx.x % p.nwg, u0 = g * U;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
-  const int CT = ncol / 16;
-  const long ldy = (long)p.dirs * H, ldg = (long)p.dirs * NW * H;
-  float *Rs = smem;                      // [ncol][LDR]
-  float *red = Rs + (long)ncol * LDR;    // [4][Npad][ncol]
-  const float *Wd = p.w + d * p.pl_stride;
-  const float *R = Wd + p.r_off;
-  if (tid == 0) bad_lds = 0;
-  for (int idx = tid; idx < ncol * H; idx += NT) {
-    const int c = idx / H, k = idx - c * H;
-    float v = 0.f;
-    if (c < NW * U) {
-      const int gt = c / U, u = c - gt * U;
-      v = R[(long)(gt * H + u0 + u) * H + k];
-    }
-    Rs[c * LDR + k] = v;
-  }
-  // pointwise item of this thread: row n, units u0+4q .. u0+4q+3
-  const int Q = U / 4, items = N * Q;
-  const bool has_item = tid < items;
-  const int in_ = has_item ? tid / Q : 0, iq = has_item ? tid - in_ * Q : 0;
-  const int ucol = u0 + 4 * iq;
-  floatx4 cst = {0.f, 0.f, 0.f, 0.f}, hpv = cst, gin[NW], bR[NW];
-#pragma unroll
-  for (int q = 0; q < NW; q++) {
-    bR[q] = (MODE == kGru && has_item) ? ld4(Wd + p.bR_off + q * H + ucol) : floatx4{0.f, 0.f, 0.f, 0.f};
-    gin[q] = floatx4{0.f, 0.f, 0.f, 0.f};
-  }
-  if (has_item) {  // prefetch the input projection of the first step
-    const int t = d == 0 ? 0 : T - 1;
-#pragma unroll
-    for (int q = 0; q < NW; q++) gin[q] = ld4(p.G + ((long)t * N + in_) * ldg + (long)d * NW * H + q * H + ucol);
-  }
-  __syncthreads();
-  int bad = 0;
-  const int KG = H / 16;
-  const int KGW = (KG + 3) / 4;  // k-groups per wave
-  const unsigned step_bytes = (unsigned)((long)N * ldy * sizeof(float));
-  unsigned *myflag = p.flags + d * p.nwg + g;
-  for (int k = 0; k < T; k++) {
-    const int t = d == 0 ? k : T - 1 - k, tp = d == 0 ? t - 1 : t + 1;
-    floatx4 acc[RT][kMaxCT];
-#pragma unroll
-    for (int a = 0; a < RT; a++)
-#pragma unroll
-      for (int b = 0; b < kMaxCT; b++) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-    REC_TRACE(k, 0);
-    if (k > 0) {
-      if (p.sync == kSyncFlag) wait_flags(p.flags + d * p.nwg, p.nwg, (unsigned)k, p.err, bad, &bad_lds);
-      REC_TRACE(k, 1);
-      const auto rs = rsrc(p.y + (long)tp * N * ldy, step_bytes);
-      for (int c0 = 0; c0 < KGW; c0 += CH) {
-        u32x4 af[RT][CH];
-        load_frags<RT, CH>(af, rs, ldy, (long)d * H, c0, KG, N, kSyncFlag, p.err, bad);
-        if (p.sync == kSyncData) settle_all<RT, CH>(af, rs, ldy, (long)d * H, c0, KG, N, p.err, bad);
-        if (p.trace) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          REC_TRACE(k, 2);
-        }
-#pragma unroll
-        for (int i = 0; i < CH; i++) {
-          const int kg = w + 4 * (c0 + i);
-          if (kg < KG) {
-#pragma unroll
-            for (int ct = 0; ct < kMaxCT; ct++) {
-              if (ct < CT) {
-                const floatx4 b = ld4(Rs + (ct * 16 + fr) * LDR + kg * 16 + fq * 4);
-#pragma unroll
-                for (int s = 0; s < 4; s++)
-#pragma unroll
-                  for (int rt = 0; rt < RT; rt++)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(af[rt][i][s]), b[s],
-                                                                       acc[rt][ct], 0, 0, 0);
-              }
-            }
-          }
-        }
-      }
-    }
-    // cross-wave K reduction through LDS
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-      for (int ct = 0; ct < kMaxCT; ct++)
-        if (ct < CT)
-#pragma unroll
-          for (int r = 0; r < 4; r++)
-            red[((long)w * p.Npad + rt * 16 + fq * 4 + r) * ncol + ct * 16 + fr] = acc[rt][ct][r];
-    __syncthreads();
-    REC_TRACE(k, 3);
-    floatx4 act[NW], cnew = {0.f, 0.f, 0.f, 0.f};
-    const long yrow = ((long)t * N + in_) * ldy + (long)d * H + ucol;
-    if (has_item) {
-      floatx4 rh[NW];
-#pragma unroll
-      for (int q = 0; q < NW; q++) {
-        const int c = q * U + 4 * iq;
-        rh[q] = ((ld4(red + ((long)0 * p.Npad + in_) * ncol + c) + ld4(red + ((long)1 * p.Npad + in_) * ncol + c)) +
-                 ld4(red + ((long)2 * p.Npad + in_) * ncol + c)) + ld4(red + ((long)3 * p.Npad + in_) * ncol + c);
-      }
-      floatx4 h;
-      if (MODE == kLstm) {
-        act[0] = sigm4(gin[0] + rh[0]);
-        act[1] = sigm4(gin[1] + rh[1]);
-        act[2] = tanh4(gin[2] + rh[2]);
-        act[3] = sigm4(gin[3] + rh[3]);
-        cst = act[1] * cst + act[0] * act[2];
-        cnew = cst;
-        h = act[3] * tanh4(cst);
-      } else if (MODE == kGru) {
-        act[0] = sigm4(gin[0] + rh[0] + bR[0]);
-        act[1] = sigm4(gin[1] + rh[1] + bR[1]);
-        cnew = rh[2] + bR[2];
-        act[2] = tanh4(gin[2] + act[0] * cnew);
-        h = (1.f - act[1]) * act[2] + act[1] * hpv;
-        hpv = h;
-      } else {
-        const floatx4 pre = gin[0] + rh[0];
-        if (MODE == kRelu) {
-#pragma unroll
-          for (int i = 0; i < 4; i++) h[i] = fmaxf(pre[i], 0.f);
-        } else {
-          h = tanh4(pre);
-        }
-      }
-      publish4(rsrc(p.y + (long)t * N * ldy, step_bytes), (unsigned)(((long)in_ * ldy + (long)d * H + ucol) * 4), h);
-    }
-    if (p.sync == kSyncFlag) signal_flag(myflag, (unsigned)(k + 1));
-    REC_TRACE(k, 4);
-    if (has_item) {
-      const long grow = ((long)t * N + in_) * ldg + (long)d * NW * H + ucol;
-      if (MODE == kLstm || MODE == kGru) {
-#pragma unroll
-        for (int q = 0; q < NW; q++) st4(p.G + grow + q * H, act[q]);
-        st4(p.aux + yrow, cnew);
-      }
-      if (k + 1 < T) {  // prefetch the next step's input projection
-        const int tn = d == 0 ? t + 1 : t - 1;
-#pragma unroll
-        for (int q = 0; q < NW; q++) gin[q] = ld4(p.G + ((long)tn * N + in_) * ldg + (long)d * NW * H + q * H + ucol);
-      }
-    }
-    __syncthreads();  // red[] is rewritten by the next step
-    REC_TRACE(k, 5);
-  }
-  if (bad && tid == 0) atomicOr(p.err, 1u);
-}
-
-// ---------------------------------------------------------------------------
-// backward-data recurrence
-// ---------------------------------------------------------------------------
-template <int MODE, int RT>
-__global__ __launch_bounds__(NT, 1) void rnn_bwd_rec(RecParams p) {
-  REC_TRACE_INIT;
-  constexpr int NW = MODE == kLstm ? 4 : MODE == kGru ? 3 : 1;
-  constexpr int CH = 32 / RT;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds;
-  const int H = p.H, U = p.U, N = p.N, T = p.T;
-  const int K = NW * H, LDK = K + 4;
-  const int d = blockIdx.x / p.nwg, g = blockIdx.x % p.nwg, u0 = g * U;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
-  const long ldy = (long)p.dirs * H, ldg = (long)p.dirs * NW * H;
-  float *RT_s = smem;                       // [U][LDK]: RT_s[u][kk] = R[kk][u0+u]
-  float *red = RT_s + (long)U * LDK;        // [4][Npad][16]
-  const float *Wd = p.w + d * p.pl_stride;
-  const float *R = Wd + p.r_off;
-  if (tid == 0) bad_lds = 0;
-  for (int idx = tid; idx < U * K; idx += NT) {
-    const int kk = idx / U, u = idx - kk * U;
-    RT_s[u * LDK + kk] = R[(long)kk * H + u0 + u];
-  }
-  const int Q = U / 4, items = N * Q;
-  const bool has_item = tid < items;
-  const int in_ = has_item ? tid / Q : 0, iq = has_item ? tid - in_ * Q : 0;
-  const int ucol = u0 + 4 * iq;
-  const floatx4 z4 = {0.f, 0.f, 0.f, 0.f};
-  floatx4 carry = z4;  // LSTM: dc carried to the previous step; GRU: dh*z direct term
-  floatx4 bsx[NW], bsh[NW], pg[NW], pdy = z4, pa = z4, pap = z4;
-#pragma unroll
-  for (int q = 0; q < NW; q++) bsx[q] = bsh[q] = pg[q] = z4;
-  auto prefetch = [&](int k) {
-    if (!has_item) return;
-    const int t = d == 0 ? k : T - 1 - k, tp = d == 0 ? t - 1 : t + 1;
-    const long yrow = ((long)t * N + in_) * ldy + (long)d * H + ucol;
-    const long grow = ((long)t * N + in_) * ldg + (long)d * NW * H + ucol;
-    const long prow = ((long)tp * N + in_) * ldy + (long)d * H + ucol;
-    pdy = ld4(p.dy + yrow);
-    if (MODE == kLstm || MODE == kGru) {
-#pragma unroll
-      for (int q = 0; q < NW; q++) pg[q] = ld4(p.G + grow + q * H);
-      pa = ld4(p.aux + yrow);
-    }
-    if (MODE == kLstm) pap = k > 0 ? ld4(p.aux + prow) : z4;
-    else if (MODE == kGru) pap = k > 0 ? ld4(p.y + prow) : z4;
-    else pap = ld4(p.y + yrow);
-  };
-  prefetch(T - 1);
-  __syncthreads();
-  int bad = 0;
-  const int KG = K / 16;
-  const int KGW = (KG + 3) / 4;
-  const unsigned step_bytes = (unsigned)((long)N * ldg * sizeof(float));
-  unsigned *myflag = p.flags + d * p.nwg + g;
-  for (int k = T - 1; k >= 0; k--) {
-    const int t = d == 0 ? k : T - 1 - k;       // forward-order index k
-    const int tn = d == 0 ? t + 1 : t - 1;      // processed just before (k+1)
-    const unsigned epoch = (unsigned)(T - k);   // number of steps published so far
-    floatx4 acc[RT];
-#pragma unroll
-    for (int a = 0; a < RT; a++) acc[a] = z4;
-    const int ks = T - 1 - k;
-    REC_TRACE(ks, 0);
-    if (k < T - 1) {
-      if (p.sync == kSyncFlag) wait_flags(p.flags + d * p.nwg, p.nwg, epoch - 1, p.err, bad, &bad_lds);
-      REC_TRACE(ks, 1);
-      const auto rs = rsrc(p.E + (long)tn * N * ldg, step_bytes);
-      for (int c0 = 0; c0 < KGW; c0 += CH) {
-        u32x4 af[RT][CH];
-        load_frags<RT, CH>(af, rs, ldg, (long)d * K, c0, KG, N, kSyncFlag, p.err, bad);
-        if (p.sync == kSyncData) settle_all<RT, CH>(af, rs, ldg, (long)d * K, c0, KG, N, p.err, bad);
-        if (p.trace) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          REC_TRACE(ks, 2);
-        }
-#pragma unroll
-        for (int i = 0; i < CH; i++) {
-          const int kg = w + 4 * (c0 + i);
-          if (kg < KG) {
-            floatx4 b = z4;
-            if (fr < U) b = ld4(RT_s + fr * LDK + kg * 16 + fq * 4);
-#pragma unroll
-            for (int s = 0; s < 4; s++)
-#pragma unroll
-              for (int rt = 0; rt < RT; rt++)
-                acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(af[rt][i][s]), b[s], acc[rt], 0, 0, 0);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) red[((long)w * p.Npad + rt * 16 + fq * 4 + r) * 16 + fr] = acc[rt][r];
-    __syncthreads();
-    REC_TRACE(ks, 3);
-    floatx4 dxk[NW];
-    const long grow = ((long)t * N + in_) * ldg + (long)d * NW * H + ucol;
-    const auto rsE = rsrc(p.E + (long)t * N * ldg, step_bytes);
-    const unsigned eoff = (unsigned)(((long)in_ * ldg + (long)d * NW * H + ucol) * 4);
-    if (has_item) {
-      const floatx4 dhr = ((ld4(red + ((long)0 * p.Npad + in_) * 16 + 4 * iq) + ld4(red + ((long)1 * p.Npad + in_) * 16 + 4 * iq)) +
-                           ld4(red + ((long)2 * p.Npad + in_) * 16 + 4 * iq)) + ld4(red + ((long)3 * p.Npad + in_) * 16 + 4 * iq);
-      floatx4 dh = pdy + dhr;
-      if (MODE == kLstm) {
-        const floatx4 ig = pg[0], fg = pg[1], gg = pg[2], og = pg[3];
-        const floatx4 tc = tanh4(pa);
-        const floatx4 dO = dh * tc;
-        const floatx4 dc = dh * og * (1.f - tc * tc) + carry;
-        const floatx4 dpi = dc * gg * ig * (1.f - ig);
-        const floatx4 dpf = dc * pap * fg * (1.f - fg);
-        const floatx4 dpg = dc * ig * (1.f - gg * gg);
-        const floatx4 dpo = dO * og * (1.f - og);
-        carry = dc * fg;
-        publish4(rsE, eoff, dpi);
-        publish4(rsE, eoff + 4 * H, dpf);
-        publish4(rsE, eoff + 8 * H, dpg);
-        publish4(rsE, eoff + 12 * H, dpo);
-        bsx[0] += dpi; bsx[1] += dpf; bsx[2] += dpg; bsx[3] += dpo;
-      } else if (MODE == kGru) {
-        dh += carry;
-        const floatx4 r = pg[0], z = pg[1], nn = pg[2];
-        const floatx4 dn = dh * (1.f - z), dz = dh * (pap - nn);
-        const floatx4 dpn = dn * (1.f - nn * nn);
-        const floatx4 dpr = dpn * pa * r * (1.f - r);
-        const floatx4 dpz = dz * z * (1.f - z);
-        carry = dh * z;
-        dxk[0] = dpr; dxk[1] = dpz; dxk[2] = dpn;
-        publish4(rsE, eoff, dpr);
-        publish4(rsE, eoff + 4 * H, dpz);
-        publish4(rsE, eoff + 8 * H, dpn * r);
-        bsx[0] += dpr; bsx[1] += dpz; bsx[2] += dpn;
-        bsh[0] += dpr; bsh[1] += dpz; bsh[2] += dpn * r;
-      } else {
-        floatx4 der;
-#pragma unroll
-        for (int i = 0; i < 4; i++) der[i] = MODE == kRelu ? (pap[i] > 0.f ? 1.f : 0.f) : (1.f - pap[i] * pap[i]);
-        const floatx4 dp = dh * der;
-        publish4(rsE, eoff, dp);
-        bsx[0] += dp;
-      }
-    }
-    if (p.sync == kSyncFlag) signal_flag(myflag, epoch);
-    REC_TRACE(ks, 4);
-    if (MODE == kGru && has_item) {
-#pragma unroll
-      for (int q = 0; q < NW; q++) st4(p.DX + grow + q * H, dxk[q]);
-    }
-    if (k > 0) prefetch(k - 1);
-    __syncthreads();
-    REC_TRACE(ks, 5);
-  }
-  // bias partial sums: reduce over n in a fixed order through LDS
-  float *bs = red;  // reuse: [2][N][U][NW] floats
-  if (has_item) {
-#pragma unroll
-    for (int q = 0; q < NW; q++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const long base = ((long)in_ * U + 4 * iq + i) * NW + q;
-        bs[base] = bsx[q][i];
-        bs[(long)N * U * NW + base] = (MODE == kGru) ? bsh[q][i] : bsx[q][i];
-      }
-  }
-  __syncthreads();
-  for (int q = tid; q < 2 * NW * U; q += NT) {
-    const int part = q / (NW * U), rem = q - part * NW * U, gt = rem / U, u = rem - gt * U;
-    float s = 0.f;
-    for (int n = 0; n < N; n++) s += bs[(long)part * N * U * NW + ((long)n * U + u) * NW + gt];
-    p.bias[((long)d * 2 + part) * NW * H + gt * H + u0 + u] = s;
-  }
-  if (bad && tid == 0) atomicOr(p.err, 1u);
-}
-
-
-// ---------------------------------------------------------------------------
-// v4: XCD-local recurrences
-// ---------------------------------------------------------------------------
-// Grid = 8 * nwg; block b works as (dir = b & 7, g = b >> 3) when b & 7 < dirs,
-// the others exit at once.  Under the observed round-robin dispatch the nwg
-// (<= 32) workgroups of one direction then share one XCD and its L2, so the
-// per-step all-gather of h (or dGates) is served by that L2 instead of the
-// fabric.  This is checked, never assumed: every workgroup publishes its
-// HW_REG_XCC_ID through the placement-independent form, and only when ALL
-// workgroups of a direction read one id does that direction hand off through
-// its L2 (plain payload and flag stores, which stay in the shared L2; sc1
-// loads, which bypass the reading CU's L1).  Otherwise it uses the
-// placement-independent form throughout (sc1 write-through payload and flag
-// stores after every storing wave's vmcnt(0) and a barrier, sc1 loads:
-// MI355X_MICROARCH.md "Valid forms", row 1).  Either way a step is
-//   wait for the direction's nwg epoch flags (one sc1 poll per lane, wave 0)
-//   -> sc1 16-B loads of the previous step straight into MFMA A registers
-//   -> v_mfma_f32_16x16x4_f32 over the LDS-resident R slice (K split over
-//      the 4 waves, reduced through LDS)
-//   -> pointwise cell math, one (n, unit) element per thread
-//   -> payload stores -> vmcnt(0) -> barrier -> lane 0 epoch flag.
-// Epoch 1 is the placement probe; step k publishes epoch k + 2.
-
-__device__ __forceinline__ unsigned xcc_id() {
-  unsigned v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xfu;
-}
-
-__device__ __forceinline__ float fsigm(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float ftanh(float x) { return 2.f * fsigm(2.f * x) - 1.f; }
-
-__device__ __forceinline__ void put(float *q, float v, int local) {
-  if (local) {
-    __hip_atomic_store(reinterpret_cast<unsigned *>(q), __float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_WORKGROUP);
-  } else {
-    __hip_atomic_store(reinterpret_cast<unsigned *>(q), __float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-__device__ __forceinline__ void signal_epoch(unsigned *flag, unsigned epoch, int local) {
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // every storing wave drains
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (local) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    else __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// Placement probe: returns 1 iff every workgroup of direction d is on this XCD.
-__device__ int probe_local(const RecParams &p, int d, int g, unsigned *myflag, int &bad, int *bad_lds,
-                           int *loc_lds) {
-  unsigned *xt = p.flags + 512 + d * p.nwg;
-  const unsigned me = xcc_id() + 1u;
-  if (threadIdx.x == 0) __hip_atomic_store(xt + g, me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  signal_epoch(myflag, 1u, 0);
-  wait_flags(p.flags + d * p.nwg, p.nwg, 1u, p.err, bad, bad_lds);
-  if (threadIdx.x < 64) {
-    bool ok = true;
-    for (int i = threadIdx.x; i < p.nwg; i += 64)
-      ok &= __hip_atomic_load(xt + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == me;
-    const bool all = __all(ok);
-    if (threadIdx.x == 0) *loc_lds = (all && p.allow_local) ? 1 : 0;
-  }
-  __syncthreads();
-  return *loc_lds;
-}
-
-constexpr int kMaxEPT = 4;  // (n, unit) elements per thread: N * U <= 1024
-
-// Exchange image of one step, fragment-major: [dirs][KG][Npad][16] floats
-// (KG = 16-wide k-groups).  One MFMA A fragment (16 rows x 16 k) is 1 KB of
-// contiguous memory, so every hand-off load instruction moves whole 128-B
-// lines; producers write 16 consecutive units of a row as 64 contiguous bytes.
-// The row-major copies the rest of the layer needs (y, E) are written with
-// plain stores off the critical path.
-__device__ __forceinline__ long xoff(int d, int kg, int n, int j, int KG, int Npad) {
-  return (((long)d * KG + kg) * Npad + n) * 16 + j;
-}
-
-// Hand-off loads + MFMA body of one step with compile-time trip counts: all
-// loads first, then the MFMAs consume them in issue order, so the in-order
-// vmcnt lets the first k-groups compute while the rest are in flight.
-// Forward: acc[RT][CT] += h_{t-1}[rows][k] * R_slice^T[k][cols], K split over
-// the 4 waves (wave w: k-groups w, w+4, ...).
-template <int RT, int CT, int KGW>
-__device__ __forceinline__ void fwd_step_mfma(floatx4 (&acc)[RT][kMaxCT], __amdgpu_buffer_rsrc_t rs, long dbase,
-                                              int Npad, const float *Rs, int LDR, int w, int fr, int fq) {
-  u32x4 af[KGW][RT];
-#pragma unroll
-  for (int i = 0; i < KGW; i++)
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-      af[i][rt] = ld_sc1(rs, (unsigned)((dbase + ((long)(w + 4 * i) * Npad + rt * 16 + fr) * 16 + fq * 4) * 4));
-#pragma unroll
-  for (int i = 0; i < KGW; i++) {
-    const int kg = w + 4 * i;
-    floatx4 b[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) b[ct] = ld4(Rs + (ct * 16 + fr) * LDR + kg * 16 + fq * 4);
-#pragma unroll
-    for (int s = 0; s < 4; s++)
-#pragma unroll
-      for (int ct = 0; ct < CT; ct++)
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++)
-          acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(af[i][rt][s]), b[ct][s], acc[rt][ct],
-                                                             0, 0, 0);
-  }
-}
-
-// Backward: acc[RT] = dG_{t+1}[rows][kk] * R^T_slice[kk][units] over all nW*H
-// kk (wave w: k-groups w, w+4, ...); NA accumulator sets interleaved so no
-// MFMA waits on its predecessor, summed in a fixed order.
-template <int RT, int KGW>
-__device__ __forceinline__ void bwd_step_mfma(floatx4 (&acc)[RT], __amdgpu_buffer_rsrc_t rs, long dbase, int Npad,
-                                              const float *RT_s, int LDK, int w, int fr, int fq) {
-  constexpr int NA = (KGW % 4 == 0) ? 4 : (KGW % 2 == 0 ? 2 : 1);
-  u32x4 af[KGW][RT];
-#pragma unroll
-  for (int i = 0; i < KGW; i++)
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-      af[i][rt] = ld_sc1(rs, (unsigned)((dbase + ((long)(w + 4 * i) * Npad + rt * 16 + fr) * 16 + fq * 4) * 4));
-  floatx4 part[NA][RT];
-#pragma unroll
-  for (int a = 0; a < NA; a++)
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) part[a][rt] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const float *brow = RT_s + fr * LDK + fq * 4;
-#pragma unroll
-  for (int i0 = 0; i0 < KGW; i0 += NA) {
-    floatx4 b[NA];
-#pragma unroll
-    for (int a = 0; a < NA; a++) b[a] = ld4(brow + (w + 4 * (i0 + a)) * 16);
-#pragma unroll
-    for (int s = 0; s < 4; s++)
-#pragma unroll
-      for (int a = 0; a < NA; a++)
-#pragma unroll
-        for (int rt = 0; rt < RT; rt++)
-          part[a][rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(af[i0 + a][rt][s]), b[a][s],
-                                                             part[a][rt], 0, 0, 0);
-  }
-#pragma unroll
-  for (int rt = 0; rt < RT; rt++) {
-    floatx4 t = part[0][rt];
-#pragma unroll
-    for (int a = 1; a < NA; a++) t += part[a][rt];
-    acc[rt] = t;
-  }
-}
-
-// generic (runtime trip count) versions of the same bodies
-template <int RT>
-__device__ __forceinline__ void fwd_step_generic(floatx4 (&acc)[RT][kMaxCT], __amdgpu_buffer_rsrc_t rs, long dbase,
-                                                 int Npad, int KG, int CT, const float *Rs, int LDR, int w, int fr,
-                                                 int fq) {
-  for (int kg = w; kg < KG; kg += 4) {
-    u32x4 af[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-      af[rt] = ld_sc1(rs, (unsigned)((dbase + ((long)kg * Npad + rt * 16 + fr) * 16 + fq * 4) * 4));
-#pragma unroll
-    for (int ct = 0; ct < kMaxCT; ct++) {
-      if (ct < CT) {
-        const floatx4 b = ld4(Rs + (ct * 16 + fr) * LDR + kg * 16 + fq * 4);
-#pragma unroll
-        for (int s = 0; s < 4; s++)
-#pragma unroll
-          for (int rt = 0; rt < RT; rt++)
-            acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(af[rt][s]), b[s], acc[rt][ct], 0, 0, 0);
-      }
-    }
-  }
-}
-template <int RT>
-__device__ __forceinline__ void bwd_step_generic(floatx4 (&acc)[RT], __amdgpu_buffer_rsrc_t rs, long dbase, int Npad,
-                                                 int KG, const float *RT_s, int LDK, int w, int fr, int fq) {
-  for (int kg = w; kg < KG; kg += 4) {
-    u32x4 af[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-      af[rt] = ld_sc1(rs, (unsigned)((dbase + ((long)kg * Npad + rt * 16 + fr) * 16 + fq * 4) * 4));
-    const floatx4 b = ld4(RT_s + fr * LDK + kg * 16 + fq * 4);
-#pragma unroll
-    for (int s = 0; s < 4; s++)
-#pragma unroll
-      for (int rt = 0; rt < RT; rt++)
-        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(af[rt][s]), b[s], acc[rt], 0, 0, 0);
-  }
-}
-
-// Everything else a step reads from or writes to HBM (next step's input
-// projection / dy / saved activations, the row-major y / E copies) is issued
-// right AFTER the step's hand-off loads have been consumed, never in front of
-// them: a wave's vector memory operations complete in issue order.
-template <int MODE, int RT>
-__global__ __launch_bounds__(NT, 1) void rnn_fwd_rec4(RecParams p) {
-  REC_TRACE_INIT;
-  constexpr int NW = MODE == kLstm ? 4 : MODE == kGru ? 3 : 1;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds, loc_lds;
-  const int slot = blockIdx.x & 7, d = slot / p.xpd, g = (blockIdx.x >> 3) * p.xpd + slot % p.xpd;
-  if (d >= p.dirs || g >= p.nwg) return;
-  const int H = p.H, U = p.U, N = p.N, T = p.T, ncol = p.ncol, Npad = p.Npad;
-  const int LDR = H + 4;
-  const int u0 = g * U;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
-  const int CT = ncol / 16;
-  const long ldy = (long)p.dirs * H, ldg = (long)p.dirs * NW * H;
-  const int KG = H / 16;
-  const long xstep = (long)p.dirs * KG * Npad * 16;  // floats of one step's exchange image
-  float *Rs = smem;                      // [ncol][LDR]
-  float *red = Rs + (long)ncol * LDR;    // [4][Npad][ncol]
-  const float *Wd = p.w + d * p.pl_stride;
-  const float *R = Wd + p.r_off;
-  if (tid == 0) bad_lds = 0;
-  for (int idx = tid; idx < ncol * H; idx += NT) {
-    const int c = idx / H, k = idx - c * H;
-    float v = 0.f;
-    if (c < NW * U) {
-      const int gt = c / U, u = c - gt * U;
-      v = R[(long)(gt * H + u0 + u) * H + k];
-    }
-    Rs[c * LDR + k] = v;
-  }
-  const int items = N * U;
-  float cst[kMaxEPT], hpv[kMaxEPT], gin[kMaxEPT][NW], gnx[kMaxEPT][NW], bR[kMaxEPT][NW];
-  float act[kMaxEPT][NW], cnew[kMaxEPT], hval[kMaxEPT];
-  auto gin_load = [&](int t, float (&dst)[kMaxEPT][NW]) {
-#pragma unroll
-    for (int j = 0; j < kMaxEPT; j++) {
-      const int e = tid + j * NT, n = e / U, u = e - n * U;
-      if (e < items) {
-#pragma unroll
-        for (int q = 0; q < NW; q++) dst[j][q] = p.G[((long)t * N + n) * ldg + (long)d * NW * H + q * H + u0 + u];
-      }
-    }
-  };
-  // row-major outputs of step t: y, and for the backward pass G (activations,
-  // overwritten in place) and aux
-  auto out_store = [&](int t) {
-#pragma unroll
-    for (int j = 0; j < kMaxEPT; j++) {
-      const int e = tid + j * NT, n = e / U, u = e - n * U;
-      if (e < items) {
-        p.y[((long)t * N + n) * ldy + (long)d * H + u0 + u] = hval[j];
-        if (MODE == kLstm || MODE == kGru) {
-          const long grow = ((long)t * N + n) * ldg + (long)d * NW * H + u0 + u;
-#pragma unroll
-          for (int q = 0; q < NW; q++) p.G[grow + q * H] = act[j][q];
-          p.aux[((long)t * N + n) * ldy + (long)d * H + u0 + u] = cnew[j];
-        }
-      }
-    }
-  };
-#pragma unroll
-  for (int j = 0; j < kMaxEPT; j++) {
-    cst[j] = hpv[j] = cnew[j] = hval[j] = 0.f;
-    const int e = tid + j * NT, u = e % U;
-#pragma unroll
-    for (int q = 0; q < NW; q++) {
-      bR[j][q] = (MODE == kGru && e < items) ? Wd[p.bR_off + q * H + u0 + u] : 0.f;
-      gin[j][q] = gnx[j][q] = act[j][q] = 0.f;
-    }
-  }
-  gin_load(d == 0 ? 0 : T - 1, gin);
-  int bad = 0;
-  unsigned *myflag = p.flags + d * p.nwg + g;
-  const int local = probe_local(p, d, g, myflag, bad, &bad_lds, &loc_lds);
-  const int KGW = KG / 4;
-  const int fast = (KG % 4 == 0 && KGW * RT <= 32 && (KGW == 8 || KGW == 4)) ? CT * 100 + KGW / 2 : 0;
-  const long dbase = (long)d * KG * Npad * 16;
-  int t_prev = -1;
-  for (int k = 0; k < T && !bad; k++) {
-    const int t = d == 0 ? k : T - 1 - k, tp = d == 0 ? t - 1 : t + 1;
-    floatx4 acc[RT][kMaxCT];
-#pragma unroll
-    for (int a = 0; a < RT; a++)
-#pragma unroll
-      for (int b = 0; b < kMaxCT; b++) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-    REC_TRACE(k, 0);
-    if (k > 0) {
-      wait_flags(p.flags + d * p.nwg, p.nwg, (unsigned)(k + 1), p.err, bad, &bad_lds);
-      REC_TRACE(k, 1);
-      const auto rs = rsrc(p.xch + (long)tp * xstep, (unsigned)(xstep * 4));
-      switch (fast) {
-        case 104: fwd_step_mfma<RT, 1, 8>(acc, rs, dbase, Npad, Rs, LDR, w, fr, fq); break;
-        case 204: fwd_step_mfma<RT, 2, 8>(acc, rs, dbase, Npad, Rs, LDR, w, fr, fq); break;
-        case 304: fwd_step_mfma<RT, 3, 8>(acc, rs, dbase, Npad, Rs, LDR, w, fr, fq); break;
-        case 404: fwd_step_mfma<RT, 4, 8>(acc, rs, dbase, Npad, Rs, LDR, w, fr, fq); break;
-        case 102: fwd_step_mfma<RT, 1, 4>(acc, rs, dbase, Npad, Rs, LDR, w, fr, fq); break;
-        case 202: fwd_step_mfma<RT, 2, 4>(acc, rs, dbase, Npad, Rs, LDR, w, fr, fq); break;
-        case 302: fwd_step_mfma<RT, 3, 4>(acc, rs, dbase, Npad, Rs, LDR, w, fr, fq); break;
-        case 402: fwd_step_mfma<RT, 4, 4>(acc, rs, dbase, Npad, Rs, LDR, w, fr, fq); break;
-        default: fwd_step_generic<RT>(acc, rs, dbase, Npad, KG, CT, Rs, LDR, w, fr, fq); break;
-      }
-    }
-    asm volatile("" ::: "memory");
-    // behind the hand-off loads: last step's row-major outputs, next step's
-    // input projection
-    if (t_prev >= 0) out_store(t_prev);
-    if (k + 1 < T) gin_load(d == 0 ? t + 1 : t - 1, gnx);
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-      for (int ct = 0; ct < kMaxCT; ct++)
-        if (ct < CT)
-#pragma unroll
-          for (int r = 0; r < 4; r++)
-            red[((long)w * Npad + rt * 16 + fq * 4 + r) * ncol + ct * 16 + fr] = acc[rt][ct][r];
-    if (p.trace) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      REC_TRACE_W(k, 10);
-    }
-    __syncthreads();
-    REC_TRACE(k, 3);
-    float *xt = p.xch + (long)t * xstep;
-#pragma unroll
-    for (int j = 0; j < kMaxEPT; j++) {
-      const int e = tid + j * NT;
-      if (e >= items) continue;
-      const int n = e / U, u = e - n * U;
-      float rh[NW];
-#pragma unroll
-      for (int q = 0; q < NW; q++) {
-        const int c = q * U + u;
-        rh[q] = ((red[((long)0 * Npad + n) * ncol + c] + red[((long)1 * Npad + n) * ncol + c]) +
-                 red[((long)2 * Npad + n) * ncol + c]) + red[((long)3 * Npad + n) * ncol + c];
-      }
-      float h;
-      if (MODE == kLstm) {
-        act[j][0] = fsigm(gin[j][0] + rh[0]);
-        act[j][1] = fsigm(gin[j][1] + rh[1]);
-        act[j][2] = ftanh(gin[j][2] + rh[2]);
-        act[j][3] = fsigm(gin[j][3] + rh[3]);
-        cst[j] = act[j][1] * cst[j] + act[j][0] * act[j][2];
-        cnew[j] = cst[j];
-        h = act[j][3] * ftanh(cst[j]);
-      } else if (MODE == kGru) {
-        act[j][0] = fsigm(gin[j][0] + rh[0] + bR[j][0]);
-        act[j][1] = fsigm(gin[j][1] + rh[1] + bR[j][1]);
-        cnew[j] = rh[2] + bR[j][2];
-        act[j][2] = ftanh(gin[j][2] + act[j][0] * cnew[j]);
-        h = (1.f - act[j][1]) * act[j][2] + act[j][1] * hpv[j];
-        hpv[j] = h;
-      } else {
-        const float pre = gin[j][0] + rh[0];
-        h = MODE == kRelu ? fmaxf(pre, 0.f) : ftanh(pre);
-      }
-      hval[j] = h;
-      const int uu = u0 + u;
-      put(xt + xoff(d, uu >> 4, n, uu & 15, KG, Npad), h, local);
-    }
-    signal_epoch(myflag, (unsigned)(k + 2), local);
-    REC_TRACE(k, 4);
-#pragma unroll
-    for (int j = 0; j < kMaxEPT; j++)
-#pragma unroll
-      for (int q = 0; q < NW; q++) gin[j][q] = gnx[j][q];
-    t_prev = t;
-    __syncthreads();  // red[] is rewritten by the next step
-    REC_TRACE(k, 5);
-  }
-  if (t_prev >= 0 && !bad) out_store(t_prev);
-  if (bad && tid == 0) atomicOr(p.err, 1u);
-}
-
-template <int MODE, int RT>
-__global__ __launch_bounds__(NT, 1) void rnn_bwd_rec4(RecParams p) {
-  REC_TRACE_INIT;
-  constexpr int NW = MODE == kLstm ? 4 : MODE == kGru ? 3 : 1;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds, loc_lds;
-  const int slot = blockIdx.x & 7, d = slot / p.xpd, g = (blockIdx.x >> 3) * p.xpd + slot % p.xpd;
-  if (d >= p.dirs || g >= p.nwg) return;
-  const int H = p.H, U = p.U, N = p.N, T = p.T, Npad = p.Npad;
-  const int K = NW * H, LDK = K + 4;
-  const int KG = K / 16;
-  const long xstep = (long)p.dirs * KG * Npad * 16;
-  const int u0 = g * U;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
-  const long ldy = (long)p.dirs * H, ldg = (long)p.dirs * NW * H;
-  float *RT_s = smem;                       // [16][LDK]: RT_s[u][kk] = R[kk][u0+u], rows >= U zero
-  float *red = RT_s + (long)16 * LDK;       // [4][Npad][16]
-  const float *Wd = p.w + d * p.pl_stride;
-  const float *R = Wd + p.r_off;
-  if (tid == 0) bad_lds = 0;
-  for (int idx = tid; idx < 16 * K; idx += NT) {
-    const int kk = idx / 16, u = idx - kk * 16;
-    RT_s[u * LDK + kk] = u < U ? R[(long)kk * H + u0 + u] : 0.f;
-  }
-  const int items = N * U;
-  // per element: current step's operands (c*), the next step's (n*), and the
-  // row-major dGates of the previous step waiting to be stored (e*, dxk)
-  float carry[kMaxEPT], bsx[kMaxEPT][NW], bsh[kMaxEPT][NW], dxk[kMaxEPT][NW], eg[kMaxEPT][NW];
-  float cg[kMaxEPT][NW], cdy[kMaxEPT], ca[kMaxEPT], cap[kMaxEPT];
-  float ng[kMaxEPT][NW], ndy[kMaxEPT], na[kMaxEPT], nap[kMaxEPT];
-#pragma unroll
-  for (int j = 0; j < kMaxEPT; j++) {
-    carry[j] = cdy[j] = ca[j] = cap[j] = ndy[j] = na[j] = nap[j] = 0.f;
-#pragma unroll
-    for (int q = 0; q < NW; q++) bsx[j][q] = bsh[j][q] = cg[j][q] = ng[j][q] = dxk[j][q] = eg[j][q] = 0.f;
-  }
-  auto prefetch = [&](int k) {  // operands of forward-order step k into n*
-    const int t = d == 0 ? k : T - 1 - k, tp = d == 0 ? t - 1 : t + 1;
-#pragma unroll
-    for (int j = 0; j < kMaxEPT; j++) {
-      const int e = tid + j * NT;
-      if (e >= items) continue;
-      const int n = e / U, u = e - n * U;
-      const long yrow = ((long)t * N + n) * ldy + (long)d * H + u0 + u;
-      const long grow = ((long)t * N + n) * ldg + (long)d * NW * H + u0 + u;
-      const long prow = ((long)tp * N + n) * ldy + (long)d * H + u0 + u;
-      ndy[j] = p.dy[yrow];
-      if (MODE == kLstm || MODE == kGru) {
-#pragma unroll
-        for (int q = 0; q < NW; q++) ng[j][q] = p.G[grow + q * H];
-        na[j] = p.aux[yrow];
-      }
-      if (MODE == kLstm) nap[j] = k > 0 ? p.aux[prow] : 0.f;
-      else if (MODE == kGru) nap[j] = k > 0 ? p.y[prow] : 0.f;
-      else nap[j] = p.y[yrow];
-    }
-  };
-  auto rotate = [&]() {
-#pragma unroll
-    for (int j = 0; j < kMaxEPT; j++) {
-      cdy[j] = ndy[j]; ca[j] = na[j]; cap[j] = nap[j];
-#pragma unroll
-      for (int q = 0; q < NW; q++) cg[j][q] = ng[j][q];
-    }
-  };
-  auto e_store = [&](int t) {  // row-major dGates of step t (E; GRU also DX)
-#pragma unroll
-    for (int j = 0; j < kMaxEPT; j++) {
-      const int e = tid + j * NT;
-      if (e >= items) continue;
-      const int n = e / U, u = e - n * U;
-      const long grow = ((long)t * N + n) * ldg + (long)d * NW * H + u0 + u;
-#pragma unroll
-      for (int q = 0; q < NW; q++) p.E[grow + q * H] = eg[j][q];
-      if (MODE == kGru) {
-#pragma unroll
-        for (int q = 0; q < NW; q++) p.DX[grow + q * H] = dxk[j][q];
-      }
-    }
-  };
-  prefetch(T - 1);
-  rotate();
-  int bad = 0;
-  unsigned *myflag = p.flags + d * p.nwg + g;
-  const int local = probe_local(p, d, g, myflag, bad, &bad_lds, &loc_lds);
-  const int KGW = KG / 4;
-  const int fast = (KG % 4 == 0 && KGW * RT <= 32 &&
-                    (KGW == 32 || KGW == 24 || KGW == 16 || KGW == 12 || KGW == 8 || KGW == 4)) ? KGW : 0;
-  const long dbase = (long)d * KG * Npad * 16;
-  int t_prev = -1;
-  for (int k = T - 1; k >= 0 && !bad; k--) {
-    const int t = d == 0 ? k : T - 1 - k;
-    const int tn = d == 0 ? t + 1 : t - 1;
-    const int ks = T - 1 - k;             // steps done before this one
-    floatx4 acc[RT];
-#pragma unroll
-    for (int a = 0; a < RT; a++) acc[a] = floatx4{0.f, 0.f, 0.f, 0.f};
-    REC_TRACE(ks, 0);
-    if (ks > 0) {
-      wait_flags(p.flags + d * p.nwg, p.nwg, (unsigned)(ks + 1), p.err, bad, &bad_lds);
-      REC_TRACE(ks, 1);
-      const auto rs = rsrc(p.xch + (long)tn * xstep, (unsigned)(xstep * 4));
-      switch (fast) {
-        case 32: bwd_step_mfma<RT, 32>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 24: bwd_step_mfma<RT, 24>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 16: bwd_step_mfma<RT, 16>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 12: bwd_step_mfma<RT, 12>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 8: bwd_step_mfma<RT, 8>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 4: bwd_step_mfma<RT, 4>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        default: bwd_step_generic<RT>(acc, rs, dbase, Npad, KG, RT_s, LDK, w, fr, fq); break;
-      }
-    }
-    asm volatile("" ::: "memory");
-    // behind the hand-off loads: next step's operands, last step's row-major dGates
-    if (k > 0) prefetch(k - 1);
-    if (t_prev >= 0) e_store(t_prev);
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) red[((long)w * Npad + rt * 16 + fq * 4 + r) * 16 + fr] = acc[rt][r];
-    if (p.trace) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      REC_TRACE_W(ks, 10);
-    }
-    __syncthreads();
-    REC_TRACE(ks, 3);
-    float *xt = p.xch + (long)t * xstep;
-#pragma unroll
-    for (int j = 0; j < kMaxEPT; j++) {
-      const int e = tid + j * NT;
-      if (e >= items) continue;
-      const int n = e / U, u = e - n * U;
-      const float dhr = ((red[((long)0 * Npad + n) * 16 + u] + red[((long)1 * Npad + n) * 16 + u]) +
-                         red[((long)2 * Npad + n) * 16 + u]) + red[((long)3 * Npad + n) * 16 + u];
-      float dh = cdy[j] + dhr;
-      const int uu = u0 + u;
-      if (MODE == kLstm) {
-        const float ig = cg[j][0], fg = cg[j][1], gg = cg[j][2], og = cg[j][3];
-        const float tc = ftanh(ca[j]);
-        const float dO = dh * tc;
-        const float dc = dh * og * (1.f - tc * tc) + carry[j];
-        eg[j][0] = dc * gg * ig * (1.f - ig);
-        eg[j][1] = dc * cap[j] * fg * (1.f - fg);
-        eg[j][2] = dc * ig * (1.f - gg * gg);
-        eg[j][3] = dO * og * (1.f - og);
-        carry[j] = dc * fg;
-      } else if (MODE == kGru) {
-        dh += carry[j];
-        const float r = cg[j][0], z = cg[j][1], nn = cg[j][2];
-        const float dn = dh * (1.f - z), dz = dh * (cap[j] - nn);
-        const float dpn = dn * (1.f - nn * nn);
-        const float dpr = dpn * ca[j] * r * (1.f - r);
-        const float dpz = dz * z * (1.f - z);
-        carry[j] = dh * z;
-        dxk[j][0] = dpr; dxk[j][1] = dpz; dxk[j][2] = dpn;
-        eg[j][0] = dpr; eg[j][1] = dpz; eg[j][2] = dpn * r;
-        bsh[j][0] += dpr; bsh[j][1] += dpz; bsh[j][2] += dpn * r;
-      } else {
-        const float der = MODE == kRelu ? (cap[j] > 0.f ? 1.f : 0.f) : (1.f - cap[j] * cap[j]);
-        eg[j][0] = dh * der;
-      }
-#pragma unroll
-      for (int q = 0; q < NW; q++) {
-        const int kk = q * H + uu;
-        put(xt + xoff(d, kk >> 4, n, kk & 15, KG, Npad), eg[j][q], local);
-        bsx[j][q] += (MODE == kGru) ? dxk[j][q] : eg[j][q];
-      }
-    }
-    signal_epoch(myflag, (unsigned)(ks + 2), local);
-    REC_TRACE(ks, 4);
-    rotate();
-    t_prev = t;
-    __syncthreads();
-    REC_TRACE(ks, 5);
-  }
-  if (t_prev >= 0 && !bad) e_store(t_prev);
-  // bias partial sums: reduce over n in a fixed order through LDS
-  float *bs = red;  // reuse: [2][N][U][NW] floats (fits: see lds sizing)
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kMaxEPT; j++) {
-    const int e = tid + j * NT;
-    if (e >= items) continue;
-    const int n = e / U, u = e - n * U;
-#pragma unroll
-    for (int q = 0; q < NW; q++) {
-      const long base = ((long)n * U + u) * NW + q;
-      bs[base] = bsx[j][q];
-      bs[(long)N * U * NW + base] = (MODE == kGru) ? bsh[j][q] : bsx[j][q];
-    }
-  }
-  __syncthreads();
-  for (int q = tid; q < 2 * NW * U; q += NT) {
-    const int part = q / (NW * U), rem = q - part * NW * U, gt = rem / U, u = rem - gt * U;
-    float s = 0.f;
-    for (int n = 0; n < N; n++) s += bs[(long)part * N * U * NW + ((long)n * U + u) * NW + gt];
-    p.bias[((long)d * 2 + part) * NW * H + gt * H + u0 + u] = s;
-  }
-  if (bad && tid == 0) atomicOr(p.err, 1u);
-}
-
-// ---------------------------------------------------------------------------
-// v6 backward: reduce-scatter hand-off, split-fp16 MFMA
-// ---------------------------------------------------------------------------
-// WG (dir, g) owns units u0..u0+U-1 and the K = nW*U rows of R that feed those
-// units' gates.  Per step it
-//   (1) sums the partial dh of its units from every producer WG of its
-//       direction (published the step before; fixed summation order),
-//   (2) does the pointwise cell backward of its (n, unit) elements (one per
-//       thread) -> dGates [N x K],
-//   (3) multiplies dGates [16 x K] by its R rows [K x H] on the matrix cores,
-//       every wave owning H/4 output columns (no cross-wave reduction), and
-//   (4) publishes that partial dh of ALL H units, fp32, in the MFMA C-fragment
-//       layout [producer][col tile][lane][4] (1 KB per 16 x 16 tile).
-// Per WG and step 32 KB are read and 32 KB written (BLSTM-512, N=16) instead of
-// the 128 KB dGates all-gather of v4.
-//
-// Split-fp16 products ("fp16x3"): both operands are scaled by powers of two
-// (R slice: one exponent per WG, from its max |R|; dGates: one exponent per
-// row, from the row's max over the WG's K columns) so the largest magnitude
-// lands in [2^13, 2^14), and split as x = hi + lo with hi = fp16(x),
-// lo = fp16(x - hi).  acc += hi_a hi_b + hi_a lo_b + lo_a hi_b on
-// v_mfma_f32_16x16x32_f16 (products exact, fp32 accumulation), then the exact
-// power-of-two unscale.  Each operand keeps 22 significant bits relative to
-// its row / slice maximum; the dropped lo*lo term is 2^-22 of it -- the same
-// order as fp32 rounding of the accumulated terms.  5.3x fewer MFMA cycles
-// than v_mfma_f32_16x16x4_f32 for the same product.
-//
-// R lives in registers for the whole launch (the B fragments of the wave's
-// H/64 column tiles, hi and lo); dGates goes through a 4.5 KB LDS image.
-// Hand-off as v4 (sc1 payload stores, vmcnt(0), barrier, sc1 epoch flag;
-// sc1 loads) into a per-step image that is never rewritten within a launch.
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-// products of the v6 recurrences: split-fp16 (fp32-class) or bf16
-enum { kPrecX3 = 0, kPrecBf16 = 1, kPrecX3S = 2 };
-// kPrecX3S: split-fp16 with the hi and lo parts stacked in ONE 16-row MFMA
-// operand -- for row groups of <= 8 sequences, whose tiles leave rows 8..15
-// empty: A = [hi rows 0..7; lo rows 0..7], acc += A B_hi + A B_lo, then row r
-// + row r + 8 = hi B_hi + hi B_lo + lo B_hi + lo B_lo (all four terms: 2 MFMAs
-// per block instead of 3, and the lo x lo term the 3-MFMA form drops)
-
-// max over each aligned group of U (8, 16, 32) lanes, all lanes active
-__device__ __forceinline__ float group_maxU(float v, int U) {
-  v = U > 8 ? group_max16(v) : group_max8(v);
-  if (U > 16) v = fmaxf(v, __shfl_xor(v, 16));
-  return v;
-}
-
-
-// v6 flag words: one 128-B line per (direction, workgroup), so that the
-// producers' flag stores and the consumers' polls spread over L2 / memory
-// channels instead of hammering one line.
-constexpr int kFlagStride = 32;  // words
-// word of the flag area where an XCD-pinned backward recurrence's workgroups
-// OR in 1 << XCC_ID (words 1008 / 1009: weight-gradient tile counters)
-constexpr int kXcdWord = 1016;
-constexpr int kResWord = 1017;  // v6 recurrence: workgroups resident so far (beside_recurrence)
-constexpr int kGateWord = 1018;  // blocks of its residency gate that left (rnn_resident_gate)
-// the named words: apart, clear of the tile and item counters (1008..1014)
-// and inside the words zeroed before every launch (v6 flag lines start at 1024)
-static_assert(kXcdWord > 1014 && kXcdWord < kResWord && kResWord < kGateWord && kGateWord < 1024,
-              "named flag words: distinct, above the counters, below 1024");
-__device__ __forceinline__ unsigned *flag6(const RecParams &p, int grp, int d, int g, int nwg) {
-  return p.flags + 1024 + (((long)grp * p.dirs + d) * nwg + g) * kFlagStride;
-}
-// aggregated epoch of (row group, direction) for the streamed GEMMs of an
-// XCD-pinned recurrence: one line each, 256 lines past the flag lines
-__device__ __forceinline__ unsigned *agg_flag6(const RecParams &p, int grp, int d) {
-  return p.flags + 1024 + (256 + (long)grp * p.dirs + d) * kFlagStride;
-}
-__device__ __forceinline__ void wait_flags6(const unsigned *f0, int nwg, unsigned epoch, unsigned *err, int &bad,
-                                            int *bad_lds, int sleep = 1) {
-  if (threadIdx.x < 64) {
-    int spins = 0;
-    while (true) {
-      bool ok = true;
-      for (int i = threadIdx.x; i < nwg; i += 64)
-        ok &= __hip_atomic_load(f0 + (long)i * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= epoch;
-      if (__all(ok)) break;
-      if (++spins > kSpinLimit ||
-          ((spins & 255) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-        bad = 1;
-        if (threadIdx.x == 0) {
-          *bad_lds = 1;
-          if (spins > kSpinLimit) atomicOr(err, 0x10000u);  // this wait ran out of time itself
-        }
-        break;
-      }
-      if (sleep) __builtin_amdgcn_s_sleep(1);
-    }
-  }
-  __syncthreads();
-  if (*bad_lds) bad = 1;
-}
-// Per-wave wait (the forward's flagged hand-off): a wave waits only for the
-// producers whose rows IT loads -- lane j polls producer prod (-1: none) --
-// and goes on to its own loads and MFMAs while the other waves still wait, so
-// the hand-off of the last producer to publish costs only the loads of the
-// waves that read it.  No workgroup barrier (the step's next one follows the
-// K reduction); a timeout sets *bad_lds for the barrier after.
-__device__ __forceinline__ bool wave_wait_prod(const unsigned *f0, int prod, unsigned epoch, unsigned *err,
-                                               int *bad_lds, int sleep) {
-  int spins = 0;
-  while (true) {
-    const bool ok =
-        prod < 0 || __hip_atomic_load(f0 + (long)prod * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= epoch;
-    if (__all(ok)) return true;
-    if (++spins > kSpinLimit ||
-        ((spins & 255) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-      if ((threadIdx.x & 63) == 0) *bad_lds = 1;
-      return false;
-    }
-    if (sleep) __builtin_amdgcn_s_sleep(1);
-  }
-}
-
-// Placement probe of a v6 launch in XCD-slot mapping: 1 iff every workgroup of
-// direction d reads the same HW_REG_XCC_ID (then the hand-off may stay in that
-// XCD's L2: plain payload and flag stores, sc1 loads).  Publishes epoch 1.
-__device__ int probe6(const RecParams &p, int grp, int d, int g, int nwg, int &bad, int *bad_lds, int *loc_lds) {
-  unsigned *ids = p.flags + 512 + (grp * p.dirs + d) * nwg;
-  const unsigned me = xcc_id() + 1u;
-  if (threadIdx.x == 0) __hip_atomic_store(ids + g, me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  signal_epoch(flag6(p, grp, d, g, nwg), 1u, 0);
-  wait_flags6(flag6(p, grp, d, 0, nwg), nwg, 1u, p.err, bad, bad_lds);
-  if (threadIdx.x < 64) {
-    bool ok = true;
-    for (int i = threadIdx.x; i < nwg; i += 64)
-      ok &= __hip_atomic_load(ids + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == me;
-    const bool all = __all(ok);
-    if (threadIdx.x == 0) *loc_lds = all ? 1 : 0;
-  }
-  __syncthreads();
-  return *loc_lds;
-}
-
-// 4-byte LDS-DMA (global_load_lds_dword): lane l's dword to LDS byte address
-// lds + 4 l.  Inline asm, so that the compiler's wait-count pass does not see
-// it: a pending LDS-DMA there merges into the other waves' code paths of
-// the same kernel and turns their exact vmcnt waits into vmcnt(0).  The
-// issuing wave waits for it with explicit s_waitcnt and reads none of it.
-// M0 (a reserved register) is saved and restored inside the statement.
-__device__ __forceinline__ void dma_lds_dword(const float *g, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(g), "s"(lds)
-      : "memory");
-}
-
-// the same, system-coherent (sc1): data written by another XCD while this
-// kernel runs (a concurrent producer's write-through stores)
-__device__ __forceinline__ void dma_lds_dword_sc1(const void *g, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off sc1\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(g), "s"(lds)
-      : "memory");
-}
-
-// A system-coherent 4-byte load that has landed when the statement ends, and
-// a write-through 4-byte store, both invisible to the compiler's wait-count
-// pass: memory operations it can see on the IO waves' paths merge into the
-// hand-off waves' paths at the barriers and make their exact waits
-// conservative (measured: a forward with such polls 2.06 -> 2.4 us/step).
-__device__ __forceinline__ unsigned ld_u32_sc1_now(const unsigned *g) {
-  unsigned v;
-  asm volatile("global_load_dword %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(g) : "memory");
-  return v;
-}
-__device__ __forceinline__ void st_u32_sc1(unsigned *g, unsigned v) {
-  asm volatile("global_store_dword %0, %1, off sc1" ::"v"(g), "v"(v) : "memory");
-}
-
-// Workgroup barrier for LDS hand-offs.  RAW = true: the LDS writes drained
-// and s_barrier, without __syncthreads' fence -- with LDS-DMA in flight the
-// fence waits for every outstanding vector memory operation (vmcnt(0)),
-// which would turn the IO waves' G fetch three steps ahead into one step and
-// hold the hand-off waves on their own stores.  Only for barriers that order
-// LDS traffic alone.
-template <bool RAW>
-__device__ __forceinline__ void lds_barrier() {
-  if constexpr (RAW) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  } else {
-    __syncthreads();
-  }
-}
-
-// exponent s with max * 2^s in [2^13, 2^14) (s = 14 for max == 0)
-__device__ __forceinline__ int split_exp(float mx) {
-  int e = 0;
-  (void)frexpf(mx, &e);
-  return 14 - e;
-}
-
-__device__ __forceinline__ void split16(float x, _Float16 &hi, _Float16 &lo) {
-  hi = (_Float16)x;
-  lo = (_Float16)(x - (float)hi);
-}
-
-// Generalisation (row groups, wide workgroups, bf16): the N sequences are
-// split into RG = ceil(N / 16) groups of 16 rows, each an independent
-// recurrence on its own dirs x NWG workgroups, flag lines and exchange images
-// (block b -> direction b % dirs, workgroup (b / dirs) % NWG, group
-// b / (dirs NWG)); a workgroup of NTH = 256 or 512 threads owns U = 8, 16 or
-// 32 units (one (row, unit) element per thread, NTH / 64 waves each owning
-// H / (16 NTH / 64) output column tiles).  P = kPrecBf16 multiplies bf16
-// dGates by a bf16 R slice instead of the split-fp16 pair (one MFMA per
-// block, no scaling; partial dh stay fp32).
-#ifndef KCTC_PIPE_STK
-#define KCTC_PIPE_STK 1
-#endif
-// stacked backward: partial-dh stores pipelined behind the next tile's MFMAs
-constexpr bool kPipeStk = KCTC_PIPE_STK != 0;
-#ifndef KCTC_EARLY_E
-#define KCTC_EARLY_E 1
-#endif
-// bf16 backward: the previous step's dGates stores under the hand-off loads
-constexpr bool kEarlyE = KCTC_EARLY_E != 0;
-template <int MODE, int U, int H, int NTH, int P>
-__global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
-  REC_TRACE_INIT;
-  constexpr int NW = MODE == kLstm ? 4 : 3;
-  constexpr int NWV = NTH / 64;
-  constexpr int K = NW * U, KB = (K + 31) / 32, AP = KB * 32 + 8;  // A image row pitch (halves)
-  constexpr int CTW = H / (16 * NWV), CTT = H / 16, NWG = H / U;
-  static_assert(CTW * 16 * NWV == H, "output column tiles per wave");
-  static_assert(16 * U <= NTH, "one (row, unit) element per thread");
-  constexpr int POS = 4 * U;       // 16-B chunks of the own column tiles per producer
-  constexpr int NGRP = NTH / POS;  // producer groups
-  constexpr int PER = NWG / NGRP;  // producers summed per group
-  static_assert(NWG % NGRP == 0, "producer groups");
-  constexpr bool BF = P == kPrecBf16;
-  constexpr bool STK = P == kPrecX3S;  // dGates hi / lo stacked in one 16-row A image (groups of <= 8 rows)
-  // split-fp16: the cell's coefficients before the hand-off (see kc below);
-  // bf16 (configs[4], every wave an element wave) measured faster with the
-  // whole pointwise backward in the cell (3.65 vs 3.46 us/step)
-  constexpr bool PRE = !BF;
-  using AT = typename std::conditional<BF, __bf16, _Float16>::type;
-  using AV = typename std::conditional<BF, bf16x8, halfx8>::type;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds, loc_lds;
-  __shared__ int rowexp[16];
-  __shared__ float wmax[NWV];
-  // xpd = 1: XCD-slot mapping (block b -> direction b & 7, so a direction's 32
-  // workgroups share one XCD under round-robin dispatch; checked by probe6;
-  // one row group only); else block b -> (group, workgroup, direction)
-  const int dirs = p.dirs;
-  const int d = p.xpd ? (blockIdx.x & 7) % dirs : blockIdx.x % dirs;
-  const int g = p.xpd ? (blockIdx.x >> 3) : (blockIdx.x / dirs) % NWG;
-  const int grp = p.xpd ? (blockIdx.x & 7) / dirs : blockIdx.x / (dirs * NWG);
-  if (d >= dirs || g >= NWG || grp >= p.rg) return;
-  // resident: counted for the exchange's residency gate (rnn_comm_gate) and
-  // in the launch's own word for the side launches beside it (beside_recurrence)
-  if (threadIdx.x == 0) {
-    __hip_atomic_fetch_add(p.flags + kResWord, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p.reg) {
-      __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(p.reg + 4), 1ull, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_AGENT);
-      if (p.xpd) __hip_atomic_fetch_or(p.reg + 2, 1u << xcc_id(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // rnn_pinned_xcds
-    }
-  }
-  // rows n0 .. nend-1 of the batch (p.gs <= 16 of the 16 MFMA rows)
-  const int N = p.N, T = p.T, n0 = grp * p.gs, nend = min(N, n0 + p.gs);
-  const int u0 = g * U, ct_own = u0 >> 4, fr0 = u0 & 15;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
-  const long ldy = (long)dirs * H, ldg = (long)dirs * NW * H;
-  // floats per producer block (16 x H) + 256 B, so that the 1-KB chunks a
-  // consumer reads from consecutive producers fall in different L2 channels
-  // bf16 mode (p.bfpart): the partials travel as bf16 (8 B per lane and tile,
-  // summed in fp32 by the consumer), half the bytes of the fp32 images
-  const bool bfp = BF && p.bfpart;
-  const long PSTR = bfp ? (long)CTT * 64 * 2 + 64 : (long)CTT * 64 * 4 + 64;
-  const int LW = bfp ? 2 : 4;  // floats-worth per lane and tile
-  const long xgrp = (long)dirs * NWG * PSTR;  // one row group's images of a step
-  const long xstep = xgrp * p.rg;
-  AT *Ahi = reinterpret_cast<AT *>(smem);  // [16][AP]
-  AT *Alo = Ahi + 16 * AP;                 // x3 only
-  float *red = reinterpret_cast<float *>(Alo + (BF ? 0 : 16 * AP));  // [NGRP][POS][4]
-  // streamed consumer: this step's dGates tile [16][NW * U] (DX for GRU), then
-  // written through with 16-B stores after the step's signal
-  float *estg = red + (NTH * 4 > 2 * 16 * U * NW ? NTH * 4 : 2 * 16 * U * NW);
-  const float *Wd = p.w + d * p.pl_stride;
-  const float *R = Wd + p.r_off;
-  if (tid == 0) bad_lds = 0;
-  for (int i = tid; i < (BF ? 16 : 32) * AP; i += NTH) Ahi[i] = (AT)0.f;  // the image(s), padding included
-  // ---- R slice -> B fragments in registers (x3: scaled hi/lo; bf16: as is) ----
-  // K order of the dGates operand: split-fp16 paths unit-major (k = u NW + q:
-  // an element's NW gates are adjacent halves, one 8-B LDS write per part),
-  // bf16 gate-major (k = q U + u)
-  constexpr bool KUM = !BF;
-  auto rval = [&](int kk, int col) -> float {
-    if (kk >= K) return 0.f;
-    const int q = KUM ? kk % NW : kk / U, u = KUM ? kk / NW : kk - (kk / U) * U;
-    return R[(long)(q * H + u0 + u) * H + col];
-  };
-  int sB = 0;
-  if constexpr (!BF) {
-    float mx = 0.f;
-#pragma unroll
-    for (int c = 0; c < CTW; c++)
-#pragma unroll
-      for (int kb = 0; kb < KB; kb++)
-#pragma unroll
-        for (int j = 0; j < 8; j++) mx = fmaxf(mx, fabsf(rval(kb * 32 + fq * 8 + j, (w * CTW + c) * 16 + fr)));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if (lane == 0) wmax[w] = mx;
-    __syncthreads();
-    float m4 = wmax[0];
-#pragma unroll
-    for (int i = 1; i < NWV; i++) m4 = fmaxf(m4, wmax[i]);
-    sB = split_exp(m4);
-  }
-  AV bhi[CTW][KB], blo[BF ? 1 : CTW][BF ? 1 : KB];
-  if constexpr (!BF) {
-#pragma unroll
-    for (int c = 0; c < CTW; c++)
-#pragma unroll
-      for (int kb = 0; kb < KB; kb++)
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          _Float16 h, l;
-          split16(ldexpf(rval(kb * 32 + fq * 8 + j, (w * CTW + c) * 16 + fr), sB), h, l);
-          bhi[c][kb][j] = h;
-          blo[c][kb][j] = l;
-        }
-  }
-  // bf16: filled after the start-up wait (probe6) below -- filled here, hipcc
-  // sank the conversions past that wait loop with all 8 x KB x CTW fp32
-  // values live and spilled the 512-thread GRU kernel to scratch (before the
-  // step loop, but a kernel with scratch must run alone: rec6_scratch_free)
-  // ---- per-element state: thread tid <-> (row n0 + en, unit u0 + eu) ----
-  const bool has_e = tid < 16 * U;
-  const int en = tid / U, eu = tid - en * U;
-  const int n = n0 + en;
-  const bool live = has_e && n < nend;
-  float carry = 0.f, bsx[NW], bsh[NW], dxk[NW], eg[NW], cg[NW], ng[NW], cmx[NW], cme[NW];
-  float cdy = 0.f, ca = 0.f, cap = 0.f, ndy = 0.f, na = 0.f, nap = 0.f;
-  // The cell's coefficients -- everything of the pointwise backward that does
-  // not depend on the hand-off -- computed from the step's forward values
-  // after the previous step's publish (while the other producers' epochs are
-  // on their way), so that the cell after the hand-off is a few FMAs:
-  //   LSTM: dc = dh kc[0] + carry, dG_q = dc kc[1+q] (q < 3), dG_3 = dh kc[4], carry = dc kc[5]
-  //   GRU : dh += carry, dX_q = dh kc[q], dE_2 = dh kc[3], carry = dh kc[4]
-  float kc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  auto coef = [&]() {
-    if (MODE == kLstm) {
-      const float ig = cg[0], fg = cg[1], gg = cg[2], og = cg[3];
-      const float tc = ftanh(ca);
-      kc[0] = og * (1.f - tc * tc);
-      kc[1] = gg * ig * (1.f - ig);
-      kc[2] = cap * fg * (1.f - fg);
-      kc[3] = ig * (1.f - gg * gg);
-      kc[4] = tc * og * (1.f - og);
-      kc[5] = fg;
-    } else {
-      const float r = cg[0], z = cg[1], nn = cg[2];
-      const float kn = (1.f - z) * (1.f - nn * nn);
-      kc[0] = kn * ca * r * (1.f - r);
-      kc[1] = (cap - nn) * z * (1.f - z);
-      kc[2] = kn;
-      kc[3] = kn * r;
-      kc[4] = z;
-    }
-  };
-  // bias and column-maximum bookkeeping of the step's dGates, and their LDS
-  // stage for the next step's row writes
-  auto book = [&]() {
-#pragma unroll
-    for (int q = 0; q < NW; q++) {
-      bsx[q] += (MODE == kGru) ? dxk[q] : eg[q];
-      if (MODE == kGru) bsh[q] += eg[q];
-      if (live) {  // column maxima for the weight GEMMs' packed transposes
-        cmx[q] = fmaxf(cmx[q], fabsf(MODE == kGru ? dxk[q] : eg[q]));
-        if (MODE == kGru) cme[q] = fmaxf(cme[q], fabsf(eg[q]));
-      }
-    }
-    if (p.e_sc1 || (BF && p.dxt != nullptr)) {
-#pragma unroll
-      for (int q = 0; q < NW; q++) estg[en * NW * U + q * U + eu] = MODE == kGru ? dxk[q] : eg[q];
-      if (MODE == kGru && BF && p.dxt != nullptr) {
-#pragma unroll
-        for (int q = 0; q < NW; q++) estg[16 * NW * U + en * NW * U + q * U + eu] = eg[q];
-      }
-    }
-  };
-#pragma unroll
-  for (int q = 0; q < NW; q++) bsx[q] = bsh[q] = dxk[q] = eg[q] = cg[q] = ng[q] = cmx[q] = cme[q] = 0.f;
-  // this element's operand columns as per-lane pointers, opaque to the
-  // compiler: they stay in VGPRs and the kernel-argument bases die here
-  // (the loop's scalar registers spill otherwise)
-  // They start at the first step's time (forward-order step T - 1) and move
-  // one step image per prefetch / row store (the loop's time moves by tstep
-  // frames a step): no per-step index arithmetic.  The laundering leaves
-  // generic pointers (FLAT loads, which count in lgkmcnt too, so that every
-  // LDS wait before a barrier covered the HBM loads): cast back to global
-  typedef const float __attribute__((address_space(1))) *gcfp;
-  typedef float __attribute__((address_space(1))) *gfp;
-  const int t_first = d == 0 ? T - 1 : 0;
-  const long ystep = (d == 0 ? -1 : 1) * (long)N * ldy, gstep = (d == 0 ? -1 : 1) * (long)N * ldg;
-  const long yel = ((long)t_first * N + n) * ldy + (long)d * H + u0 + eu;
-  const long gel = ((long)t_first * N + n) * ldg + (long)d * NW * H + u0 + eu;
-  const float *dy_e = p.dy + yel;
-  const float *g_e = p.G + gel;
-  const float *aux_e = p.aux + yel;
-  const float *prv_e = (MODE == kLstm ? p.aux : p.y) + yel + ystep;  // the step before, in forward order
-  float *e_e = p.E + gel;
-  float *dx_e = (MODE == kGru ? p.DX : p.E) + gel;
-  asm volatile("" : "+v"(dy_e), "+v"(g_e), "+v"(aux_e), "+v"(prv_e), "+v"(e_e), "+v"(dx_e));
-  gcfp dy_p = (gcfp)dy_e, g_p = (gcfp)g_e, aux_p = (gcfp)aux_e, prv_p = (gcfp)prv_e;
-  gfp e_p = (gfp)e_e, dx_p = (gfp)dx_e;
-  auto prefetch = [&](int k) {  // operands of forward-order step k (T - 1, T - 2, ... in turn) into n*
-    if (live) {
-      ndy = *dy_p;
-#pragma unroll
-      for (int q = 0; q < NW; q++) ng[q] = g_p[q * H];
-      na = *aux_p;
-      nap = k > 0 ? *prv_p : 0.f;
-    }
-    dy_p += ystep; g_p += gstep; aux_p += ystep; prv_p += ystep;
-  };
-  auto rotate = [&]() {
-    cdy = ndy; ca = na; cap = nap;
-#pragma unroll
-    for (int q = 0; q < NW; q++) cg[q] = ng[q];
-  };
-  // bf16 packed operands (p.dxt): the step's DX tile is staged in estg and the
-  // GRU's E tile in estg2 during the cell phase; the next step writes them as
-  // 16-B bf16 chunks (DX rows; DX^T and E^T columns of 8 frames)
-  float *estg2 = estg + 16 * NW * U;
-  const bool pk = BF && p.dxt != nullptr;
-  auto pk_store = [&](int tt) {
-    if constexpr (BF) {
-      constexpr int RCH = NW * U / 8;  // 16-B row chunks per row
-      const long TNl = (long)T * N, G4 = (long)NW * H;
-      const long f0 = (long)tt * N + n0;
-      // DX rows: thread -> (row, chunk)
-      for (int i = tid; i < 16 * RCH; i += NTH) {
-        const int rn = i / RCH, ch = i - rn * RCH, q = (ch * 8) / U, u = (ch * 8) % U;
-        if (n0 + rn >= nend) continue;
-        bf16x8 v;
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = (__bf16)estg[rn * NW * U + q * U + u + j];
-        *reinterpret_cast<bf16x8 *>(p.dxr + ((long)d * TNl + f0 + rn) * G4 + q * H + u0 + u) = v;
-      }
-      // DX^T (and E^T) columns: thread -> (column, 8-frame half); aligned 16-B
-      // chunks when the 8 frames are whole, else per frame.  E^T shifted
-      // (eshift): frames of step 0 (direction 0) / T - 1 (direction 1) drop out
-      const bool vec8 = (N % 8 == 0) && (n0 % 8 == 0);
-      const int narr = (MODE == kGru || p.eshift) ? 2 : 1;
-      const long esh = p.eshift ? (d == 0 ? -(long)N : (long)N) : 0;
-      const bool edrop = p.eshift && (d == 0 ? tt == 0 : tt == T - 1);
-      for (int i = tid; i < narr * NW * U * 2; i += NTH) {
-        const int which = i / (NW * U * 2), rem = i - which * NW * U * 2, col = rem >> 1, half = rem & 1;
-        if (which && edrop) continue;
-        const float *src = (which && MODE == kGru) ? estg2 : estg;
-        __bf16 *dst = (which ? p.et : p.dxt) + ((long)d * G4 + (col / U) * H + u0 + col % U) * p.kbt64 + f0 + half * 8 +
-                      (which ? esh : 0);
-        const int r0 = half * 8;
-        if (vec8 && n0 + r0 + 8 <= nend) {
-          bf16x8 v;
-#pragma unroll
-          for (int j = 0; j < 8; j++) v[j] = (__bf16)src[(r0 + j) * NW * U + col];
-          *reinterpret_cast<bf16x8 *>(dst) = v;
-        } else {
-          for (int j = 0; j < 8; j++)
-            if (n0 + r0 + j < nend) dst[j] = (__bf16)src[(r0 + j) * NW * U + col];
-        }
-      }
-    }
-  };
-  // row-major dGates of step t (E; GRU also DX): the loop's steps in turn,
-  // e_p / dx_p move on by one step image a call
-  auto e_store = [&](int t) {
-    const gfp ep = e_p, dp = dx_p;
-    e_p += gstep; dx_p += gstep;
-    if (pk) {
-      pk_store(t);
-      return;
-    }
-    if (!live) return;
-    if (p.e_sc1) {  // DX (== E for LSTM) went out through estg already
-      if (MODE == kGru) {
-#pragma unroll
-        for (int q = 0; q < NW; q++) ep[q * H] = eg[q];
-      }
-      return;
-    }
-#pragma unroll
-    for (int q = 0; q < NW; q++) ep[q * H] = eg[q];
-    if (MODE == kGru) {
-#pragma unroll
-      for (int q = 0; q < NW; q++) dp[q * H] = dxk[q];
-    }
-  };
-  // consumer chunk of this thread: position pos (of the own column tiles'
-  // C-fragment chunks) of producers pg, pg + NGRP, ...
-  const int pos = tid % POS, pg = tid / POS;
-  const int pln = U >= 16 ? pos : (pos >> 3) * 16 + fr0 + (pos & 7);
-  const long coff = (long)grp * xgrp + (long)d * NWG * PSTR + ((long)ct_own * 64 + pln) * LW + (long)pg * PSTR;
-  // a C-fragment lane holds rows 4 (lane / 16) .. +3 of the group: quads past N
-  // are neither stored nor loaded (a group of fewer than 16 sequences moves
-  // only its own rows).  STK (transposed, U = 16): chunk j = 8 (unit / 4) +
-  // row of a tile holds units 4 (j / 8) .. +3 of row j % 8, chunks 32..63 unused
-  const bool crow_live = STK ? (pln < 32 && n0 + (pln & 7) < nend) : n0 + 4 * ((pln & 63) >> 4) < nend;
-  const bool prow_live = STK ? (fr < 8 && n0 + fr < nend) : n0 + 4 * fq < nend;
-  // where element (en, eu) finds its sum: own tile eu / 16, lane (en / 4) * 16
-  // + (eu % 16) (U = 8: compacted to 8 per row quad), register en % 4
-  const int epos = STK ? (eu >> 2) * 8 + en : (eu >> 4) * 64 + (en >> 2) * (U < 16 ? U : 16) + (eu & 15);
-  const int ereg = STK ? (eu & 3) : (en & 3);
-  prefetch(T - 1);
-  rotate();
-  if constexpr (PRE) coef();
-  int bad = 0;
-  unsigned *myflag = flag6(p, grp, d, g, NWG);
-  // XCD-slot launches keep the hand-off in the XCD's L2 (plain flag stores
-  // other XCDs do not see).  For the streamed dx GEMM running on the other
-  // XCDs, workgroup 0 of each (row group, direction) publishes ONE aggregated
-  // sc1 epoch (agg_flag6): after the first barrier of step ks it has seen every
-  // producer's epoch ks + 1, whose signals drained their rows of step ks - 2,
-  // so it stores ks + 1 ("rows of step k complete at epoch k + 3").  One line
-  // per direction instead of 32 for up to ~100 polling GEMM blocks.
-  unsigned *gflag = (p.xpd && p.e_sc1 && g == 0) ? agg_flag6(p, grp, d) : nullptr;
-  // and where it runs, for the streamed GEMM's blocks (on_pinned_xcd)
-  // (before any wait on another workgroup: a residency gate block on this XCD
-  // leaves on it, rnn_resident_gate)
-  if (p.xpd && tid == 0) atomicOr(p.flags + kXcdWord, 1u << xcc_id());
-  if (tid == 0) loc_lds = 0;
-  const int local = (p.xpd && p.allow_local) ? probe6(p, grp, d, g, NWG, bad, &bad_lds, &loc_lds) : 0;
-  if constexpr (BF) {
-    auto fill = [&]() {
-#pragma unroll
-      for (int c = 0; c < CTW; c++)
-#pragma unroll
-        for (int kb = 0; kb < KB; kb++)
-#pragma unroll
-          for (int j = 0; j < 8; j++) bhi[c][kb][j] = (__bf16)rval(kb * 32 + fq * 8 + j, (w * CTW + c) * 16 + fr);
-    };
-    fill();
-  }
-  if (trc_ && tid == 0) trc_[9] = (unsigned long long)(local + 1);  // step 0, slot 9
-  // Self-tagged hand-off (fp32 partials, XCD-local slot, ring of two step
-  // images set to tag 1 before the launch): the producer's partial-dh words
-  // carry ((step >> 1) & 1) in their LSB, the consumers re-load a chunk until
-  // all its words carry the step's tag.  No per-step drain, signal barrier,
-  // flag store or flag poll -- the poll IS the payload load.  Ring safety as
-  // before: a producer writes slot ks % 2 only after it has read every
-  // consumer's step ks - 1 words, stored after that consumer's loads of step
-  // ks - 2 had returned.
-  const bool dtag = !BF && p.dtag && local && p.ring == 2;
-  // step t's DX rows for a streaming consumer on other XCDs, from the LDS
-  // stage: written through (sc1) as whole 16-B chunks, 4 lanes per
-  // contiguous 64-B run (4-B write-through stores per element cost ~8 us per
-  // step); the next signal drains them, so they are complete at epoch t + 3
-  auto e_sc1_store = [&](int tt) {
-    constexpr int CPR = NW * U / 4;  // chunks per row
-    // self-tagged (issued after the first barrier): the LAST 16 CPR threads,
-    // i.e. the waves past the element waves when there are any, store while
-    // the element waves do the cell
-    const int et = dtag ? tid - (NTH - 16 * CPR) : tid;
-    const int rn = et >= 0 ? et / CPR : 16, c = et - rn * CPR;
-    if (rn < 16 && n0 + rn < nend) {
-      const int q = (c * 4) / U, u = (c * 4) % U;
-      const u32x4 v = *reinterpret_cast<const u32x4 *>(estg + rn * NW * U + c * 4);
-      const int off = (int)(((long)(n0 + rn) * ldg + (long)d * NW * H + q * H + u0 + u) * 4);
-      __builtin_amdgcn_raw_buffer_store_b128(v, rsrc(p.DX + (long)tt * N * ldg, (unsigned)(N * ldg * 4)), off, 0, 16);
-    }
-  };
-  int t_prev = -1;
-  for (int k = T - 1; k >= 0 && !bad; k--) {
-    const int t = d == 0 ? k : T - 1 - k;
-    const int ks = T - 1 - k;  // steps done before this one
-    REC_TRACE(ks, 0);
-    if (ks > 0) {
-      if (dtag) {
-        // self-tagged: no flags; the poll below is the wait
-      } else {
-        wait_flags6(flag6(p, grp, d, 0, NWG), NWG, (unsigned)(ks + 1), p.err, bad, &bad_lds, p.poll_sleep);
-      }
-      REC_TRACE(ks, 1);
-      REC_TRACE_W(ks, 16);
-      const auto rs = rsrc(p.xch + (long)(p.ring ? (ks - 1) & 1 : ks - 1) * xstep, (unsigned)(xstep * 4));  // (ring: 2 images)
-      floatx4 sm = floatx4{0.f, 0.f, 0.f, 0.f};
-      if (bfp) {
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        u32x2 v[PER];
-        // unconditional (a dead row quad past the buffer: zeros), so that the
-        // work below overlaps them
-#pragma unroll
-        for (int i = 0; i < PER; i++)
-          v[i] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(
-                     rs, crow_live ? (int)((coff + (long)i * NGRP * PSTR) * 4) : 0x7fff0000, 0, 16 /* sc1 */));
-        if constexpr (PRE) {
-          __builtin_amdgcn_sched_barrier(0);
-          coef();  // while the hand-off loads are in flight
-          __builtin_amdgcn_sched_barrier(0);
-        } else if (kEarlyE) {
-          // bf16: the previous step's dGates rows / packed operands (its
-          // cell's estg stage, complete since the MFMA phase's barrier) while
-          // the hand-off loads are in flight, instead of after them
-          __builtin_amdgcn_sched_barrier(0);
-          e_store(t_prev);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int i = 0; i < PER; i++) {
-          const bf16x4 b = __builtin_bit_cast(bf16x4, v[i]);
-#pragma unroll
-          for (int j = 0; j < 4; j++) sm[j] += (float)b[j];
-        }
-      } else {
-        u32x4 v[PER];
-        // unconditional loads (a dead row quad at an offset past the buffer:
-        // the hardware returns zeros), so that the compiler counts them
-        // exactly and the coefficients below overlap them
-        auto hoff = [&](int i) { return crow_live ? (unsigned)((coff + (long)i * NGRP * PSTR) * 4) : 0x7fff0000u; };
-#pragma unroll
-        for (int i = 0; i < PER; i++) v[i] = ld_sc1(rs, hoff(i));
-        if constexpr (PRE) {
-          __builtin_amdgcn_sched_barrier(0);
-          coef();  // while the hand-off loads are in flight
-          // (pinned here: IR passes had sunk the coefficients past the loads' wait)
-#pragma unroll
-          for (int q = 0; q < 6; q++) asm volatile("" : "+v"(kc[q]));
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (dtag) {
-          // every word of step ks - 1 carries tag ((ks - 1) >> 1) & 1 in its
-          // LSB; a chunk still holding step ks - 3's words (the other tag) is
-          // loaded again.  4-B words are single-copy atomic, so a 16-B load
-          // that tears between the two steps is caught word by word.
-          const unsigned want = (unsigned)((ks - 1) >> 1) & 1u;
-          auto ready = [&]() {
-            unsigned bad4 = 0u;
-#pragma unroll
-            for (int i = 0; i < PER; i++) bad4 |= (v[i][0] ^ want) | (v[i][1] ^ want) | (v[i][2] ^ want) | (v[i][3] ^ want);
-            return !crow_live || (bad4 & 1u) == 0u;
-          };
-          int spins = 0;
-          while (!__all(ready())) {  // (not all there yet: the wave loads all its chunks again)
-            if (++spins > kSpinLimit ||
-                ((spins & 255) == 0 &&
-                 __builtin_amdgcn_readfirstlane(__hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))) {
-              bad = 1;
-              if (lane == 0) bad_lds = 1;
-              break;
-            }
-            if (p.poll_sleep) __builtin_amdgcn_s_sleep(1);
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < PER; i++) v[i] = ld_sc1(rs, hoff(i));
-          }
-        }
-        sm = __builtin_bit_cast(floatx4, v[0]);
-#pragma unroll
-        for (int i = 1; i < PER; i++) sm += __builtin_bit_cast(floatx4, v[i]);
-      }
-      st4(red + (long)(pg * POS + pos) * 4, sm);
-      REC_TRACE(ks, 2);
-      REC_TRACE_W(ks, 24);
-      // behind this step's hand-off loads: the write-through copies for the
-      // streamed dx GEMM -- the previous step's dGates rows (staged in LDS)
-      // and the epoch the last signal drained (step ks - 2's rows).  Issued
-      // after the signal instead, they were still in flight at the next flag
-      // poll, which waits for every older store (one vmcnt for loads and stores)
-      // (self-tagged: after the barrier below, which orders it behind the
-      // previous step's book() writes of estg -- no signal barrier in between)
-      if (p.e_sc1 && !dtag) e_sc1_store(t_prev);
-    }
-    asm volatile("" ::: "memory");
-    // behind the hand-off loads: next step's operands, last step's row-major dGates
-    if (t_prev >= 0 && !(kEarlyE && !PRE && bfp && ks > 0)) e_store(t_prev);
-    if (k > 0) prefetch(k - 1);
-    __syncthreads();
-    REC_TRACE(ks, 8);
-    if (bad_lds) bad = 1;
-    // self-tagged: every producer's words of step ks - 1 were stored after its
-    // poll of step ks - 2 had retired (in-order vmcnt) its write-through rows
-    // of step ks - 3 -> epoch ks (rows of step k out at epoch k + 3);
-    // flagged: its signal of step ks - 1 drained the rows of step ks - 2
-    if (gflag && ks > 0 && tid == 0)
-      __hip_atomic_store(gflag, (unsigned)(dtag ? ks : ks + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (dtag && p.e_sc1 && ks > 0) e_sc1_store(t_prev);
-    if (has_e) {
-      float dhr = 0.f;
-      if (ks > 0) {
-        // all NGRP reads in flight before the first add (one LDS latency,
-        // not NGRP), then the fixed-order sum
-        float rr[NGRP];
-#pragma unroll
-        for (int gg = 0; gg < NGRP; gg++) rr[gg] = red[(long)(gg * POS + epos) * 4 + ereg];
-        __builtin_amdgcn_sched_group_barrier(0x100, NGRP, 0);
-#pragma unroll
-        for (int gg = 0; gg < NGRP; gg++) dhr += rr[gg];
-      }
-      float dh = cdy + dhr;
-      if constexpr (PRE) {
-        if (MODE == kLstm) {
-          const float dc = dh * kc[0] + carry;
-          eg[0] = dc * kc[1];
-          eg[1] = dc * kc[2];
-          eg[2] = dc * kc[3];
-          eg[3] = dh * kc[4];
-          carry = dc * kc[5];
-        } else {
-          dh += carry;
-          dxk[0] = dh * kc[0]; dxk[1] = dh * kc[1]; dxk[2] = dh * kc[2];
-          eg[0] = dxk[0]; eg[1] = dxk[1]; eg[2] = dh * kc[3];
-          carry = dh * kc[4];
-        }
-      } else if (MODE == kLstm) {
-        const float ig = cg[0], fg = cg[1], gg = cg[2], og = cg[3];
-        const float tc = ftanh(ca);
-        const float dO = dh * tc;
-        const float dc = dh * og * (1.f - tc * tc) + carry;
-        eg[0] = dc * gg * ig * (1.f - ig);
-        eg[1] = dc * cap * fg * (1.f - fg);
-        eg[2] = dc * ig * (1.f - gg * gg);
-        eg[3] = dO * og * (1.f - og);
-        carry = dc * fg;
-      } else {
-        dh += carry;
-        const float r = cg[0], z = cg[1], nn = cg[2];
-        const float dn = dh * (1.f - z), dz = dh * (cap - nn);
-        const float dpn = dn * (1.f - nn * nn);
-        const float dpr = dpn * ca * r * (1.f - r);
-        const float dpz = dz * z * (1.f - z);
-        carry = dh * z;
-        dxk[0] = dpr; dxk[1] = dpz; dxk[2] = dpn;
-        eg[0] = dpr; eg[1] = dpz; eg[2] = dpn * r;
-      }
-      float m = 0.f;
-#pragma unroll
-      for (int q = 0; q < NW; q++) m = fmaxf(m, fabsf(eg[q]));
-      if constexpr (!PRE) book();
-      if constexpr (BF) {
-#pragma unroll
-        for (int q = 0; q < NW; q++) Ahi[en * AP + q * U + eu] = (__bf16)eg[q];
-      } else {
-        const int se = split_exp(group_maxU(m, U));
-        // unit-major K: the element's NW gates are halves eu NW .. eu NW + NW - 1
-        // of its row (STK: hi in row en < 8, lo in row en + 8)
-        _Float16 hh[4], hl[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) hh[q] = hl[q] = (_Float16)0.f;
-#pragma unroll
-        for (int q = 0; q < NW; q++) split16(ldexpf(eg[q], se), hh[q], hl[q]);
-        _Float16 *dhi = Ahi + en * AP + eu * NW;
-        _Float16 *dlo = STK ? Ahi + (en + 8) * AP + eu * NW : Alo + en * AP + eu * NW;
-        if (!STK || en < 8) {
-          if constexpr (NW == 4) {
-            typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<half4 *>(dhi) = half4{hh[0], hh[1], hh[2], hh[3]};
-            *reinterpret_cast<half4 *>(dlo) = half4{hl[0], hl[1], hl[2], hl[3]};
-          } else {
-#pragma unroll
-            for (int q = 0; q < NW; q++) {
-              dhi[q] = hh[q];
-              dlo[q] = hl[q];
-            }
-          }
-        }
-        if (eu == 0) rowexp[en] = se + sB;
-      }
-    }
-    REC_TRACE(ks, 12);
-    __syncthreads();
-    REC_TRACE(ks, 3);
-    if (STK && k > 0 && kPipeStk) {
-      // partial dh of all units for the next step, stacked hi / lo: tile c's
-      // four MFMAs, then -- while tile c + 1's run -- its fold, scaling, tag
-      // and 16-B store, as one straight-line block per cache policy (the
-      // store of a dead lane goes past the buffer's end and is dropped)
-      const auto ro = rsrc(p.xch + (long)(p.ring ? ks & 1 : ks) * xstep, (unsigned)(xstep * 4));
-      const long obase = (long)grp * xgrp + (long)(d * NWG + g) * PSTR;
-      const unsigned tg = (unsigned)(ks >> 1) & 1u;
-      const int e1 = -rowexp[fr & 7];
-      AV ah[KB];
-#pragma unroll
-      for (int kb = 0; kb < KB; kb++) ah[kb] = *reinterpret_cast<const AV *>(Ahi + fr * AP + kb * 32 + fq * 8);
-      auto phase = [&](auto aux_c) {
-        constexpr int aux = decltype(aux_c)::value;
-        floatx4 acc[CTW];
-#pragma unroll
-        for (int c = 0; c < CTW; c++) {
-          acc[c] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int kb = 0; kb < KB; kb++) {  // the order of the interleaved version: hi, lo per k block
-            acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bhi[c][kb], ah[kb], acc[c], 0, 0, 0);
-            acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(blo[c][kb], ah[kb], acc[c], 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < CTW; c++) {
-          floatx4 o;
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            float v = acc[c][i] + __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[c][i]), 0x128, 0xF, 0xF, true));
-            v = ldexpf(v, e1);
-            o[i] = __uint_as_float((__float_as_uint(v) & ~1u) | tg);
-          }
-          const int slot = fq * 8 + (fr & 7);
-          const int off = prow_live ? (int)((obase + ((long)(w * CTW + c) * 64 + slot) * LW) * 4) : 0x7ffffff0;
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ro, off, 0, aux);
-        }
-        // pipeline: MFMAs of tiles 0 and 1, then per tile c the fold + store
-        // of tile c - 1 ... interleaved with tile c + 1's MFMAs
-        __builtin_amdgcn_sched_group_barrier(0x008, 2 * KB, 0);  // tile 0 (2 KB MFMAs a tile)
-#pragma unroll
-        for (int c = 1; c < CTW; c++) {
-          __builtin_amdgcn_sched_group_barrier(0x008, KB, 0);  // tile c (first half)
-          __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);  // tile c - 1: fold, scale, tag
-          __builtin_amdgcn_sched_group_barrier(0x008, KB, 0);  // tile c (second half)
-          __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);   // tile c - 1: store
-        }
-        __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);  // last tile
-        __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-      };
-      if (local) phase(std::integral_constant<int, 0>{});
-      else phase(std::integral_constant<int, 16>{});
-    } else if (BF && k > 0 && kPipeStk && bfp) {
-      // bf16 with bf16 partials (configs[4]): the same pipeline -- tile c's KB
-      // MFMAs, then its bf16 pack and 8-B store behind tile c + 1's
-      const auto ro = rsrc(p.xch + (long)(p.ring ? ks & 1 : ks) * xstep, (unsigned)(xstep * 4));
-      const long obase = (long)grp * xgrp + (long)(d * NWG + g) * PSTR;
-      AV ah[KB];
-#pragma unroll
-      for (int kb = 0; kb < KB; kb++) ah[kb] = *reinterpret_cast<const AV *>(Ahi + fr * AP + kb * 32 + fq * 8);
-      auto phase = [&](auto aux_c) {
-        constexpr int aux = decltype(aux_c)::value;
-        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        floatx4 acc[CTW];
-#pragma unroll
-        for (int c = 0; c < CTW; c++) {
-          acc[c] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int kb = 0; kb < KB; kb++) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[kb], bhi[c][kb], acc[c], 0, 0, 0);
-        }
-#pragma unroll
-        for (int c = 0; c < CTW; c++) {
-          bf16x4 b;
-#pragma unroll
-          for (int i = 0; i < 4; i++) b[i] = (__bf16)acc[c][i];
-          const int off = prow_live ? (int)((obase + ((long)(w * CTW + c) * 64 + lane) * LW) * 4) : 0x7ffffff0;
-          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, b), ro, off, 0, aux);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, KB, 0);  // tile 0
-#pragma unroll
-        for (int c = 1; c < CTW; c++) {
-          __builtin_amdgcn_sched_group_barrier(0x008, KB, 0);  // tile c
-          __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // tile c - 1: bf16 pack
-          __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);   // tile c - 1: store
-        }
-        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // last tile
-        __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);
-      };
-      if (local) phase(std::integral_constant<int, 0>{});
-      else phase(std::integral_constant<int, 16>{});
-    } else if (k > 0) {  // partial dh of all units for the next step
-      floatx4 acc[CTW];
-#pragma unroll
-      for (int c = 0; c < CTW; c++) acc[c] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kb = 0; kb < KB; kb++) {
-        const AV ah = *reinterpret_cast<const AV *>(Ahi + fr * AP + kb * 32 + fq * 8);
-        if constexpr (BF) {
-#pragma unroll
-          for (int c = 0; c < CTW; c++) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bhi[c][kb], acc[c], 0, 0, 0);
-        } else if constexpr (STK) {
-          // transposed: C^T[unit][row'] = R_slice^T dG^T, row' < 8 hi, >= 8 lo
-          // (the R fragments as the A operand: same registers, A[unit][k])
-#pragma unroll
-          for (int c = 0; c < CTW; c++) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bhi[c][kb], ah, acc[c], 0, 0, 0);
-#pragma unroll
-          for (int c = 0; c < CTW; c++) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(blo[c][kb], ah, acc[c], 0, 0, 0);
-        } else {
-          const AV al = *reinterpret_cast<const AV *>(Alo + fr * AP + kb * 32 + fq * 8);
-#pragma unroll
-          for (int c = 0; c < CTW; c++) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bhi[c][kb], acc[c], 0, 0, 0);
-#pragma unroll
-          for (int c = 0; c < CTW; c++) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, blo[c][kb], acc[c], 0, 0, 0);
-#pragma unroll
-          for (int c = 0; c < CTW; c++) acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bhi[c][kb], acc[c], 0, 0, 0);
-        }
-      }
-      if constexpr (STK) {  // columns 8..15 (lo rows) onto 0..7: one DPP add (row_ror:8) per register
-#pragma unroll
-        for (int c = 0; c < CTW; c++)
-#pragma unroll
-          for (int i = 0; i < 4; i++)  // (mov_dpp with bound_ctrl: combined into one v_add_f32_dpp)
-            acc[c][i] += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(acc[c][i]), 0x128, 0xF, 0xF, true));
-      }
-      int ex[4] = {0, 0, 0, 0};
-      if constexpr (STK) {
-        const int e1 = -rowexp[fr & 7];  // one row per lane
-#pragma unroll
-        for (int i = 0; i < 4; i++) ex[i] = e1;
-      } else if constexpr (!BF) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) ex[i] = -rowexp[fq * 4 + i];
-      }
-      // a ring of >= 2 images is safe: every workgroup is a consumer of every
-      // producer, so before a producer writes slot ks % ring at step ks it saw
-      // all flags of step ks - 1, i.e. every consumer had finished reading
-      // that slot's previous contents (step ks - ring, read during ks - ring + 1)
-      const auto ro = rsrc(p.xch + (long)(p.ring ? ks & 1 : ks) * xstep, (unsigned)(xstep * 4));
-      const long obase = (long)grp * xgrp + (long)(d * NWG + g) * PSTR;
-      // fp32 partials carry the step tag ((ks >> 1) & 1) in their LSB in every
-      // mode (the self-tagged hand-off reads it; the others keep the same
-      // arithmetic, so that pinned and unpinned runs stay bit-identical)
-      const unsigned tg = (unsigned)(ks >> 1) & 1u;
-#pragma unroll
-      for (int c = 0; c < CTW; c++) {
-        floatx4 o;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          o[i] = BF ? acc[c][i] : ldexpf(acc[c][i], ex[i]);
-          if (!bfp) o[i] = __uint_as_float((__float_as_uint(o[i]) & ~1u) | tg);
-        }
-        const int slot = STK ? (fq * 8 + (fr & 7)) : lane;  // STK: compact chunks of the 8 live columns
-        const int off = (int)((obase + ((long)(w * CTW + c) * 64 + slot) * LW) * 4);
-        // local: plain stores keep the lines in the XCD's shared L2, where the
-        // consumers' sc1 loads find them; else write-through (sc1)
-        if (!prow_live) {
-        } else if (bfp) {
-          typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-          bf16x4 b;
-#pragma unroll
-          for (int i = 0; i < 4; i++) b[i] = (__bf16)o[i];
-          if (local) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, b), ro, off, 0, 0);
-          else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, b), ro, off, 0, 16);
-        } else if (local) {
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ro, off, 0, 0);
-        } else {
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ro, off, 0, 16);
-        }
-      }
-    }
-    // off the hand-off path (behind the partial-dh stores, during their
-    // drain): bias and column-maximum bookkeeping, the dGates stage for the
-    // next step's row writes (read after the publish barrier)
-    if constexpr (PRE) {
-      __builtin_amdgcn_sched_barrier(0);
-      if (has_e) book();
-    }
-    REC_TRACE(ks, 7);
-    if (!dtag) signal_epoch(myflag, (unsigned)(ks + 2), local);
-    REC_TRACE(ks, 4);
-    rotate();
-    t_prev = t;
-    REC_TRACE(ks, 5);
-  }
-  if (dtag) __syncthreads();  // the last step's book() writes of estg, before e_sc1_store reads them
-  if (t_prev >= 0 && !bad) e_store(t_prev);
-  if (!bad) {
-    if (p.e_sc1 && t_prev >= 0) e_sc1_store(t_prev);
-    signal_epoch(myflag, (unsigned)(T + 2), 0);  // the last step's rows are out
-    if (gflag) {  // every producer's last rows are out
-      wait_flags6(flag6(p, grp, d, 0, NWG), NWG, (unsigned)(T + 2), p.err, bad, &bad_lds, p.poll_sleep);
-      if (!bad && tid == 0) __hip_atomic_store(gflag, (unsigned)(T + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  // bias partial sums of this row group: reduce over its rows in a fixed
-  // order through LDS; the host adds the groups in order
-  float *bs = red;  // [2][16][U][NW] floats
-  __syncthreads();
-  if (has_e) {
-#pragma unroll
-    for (int q = 0; q < NW; q++) {
-      const long b0 = ((long)en * U + eu) * NW + q;
-      bs[b0] = live ? bsx[q] : 0.f;
-      bs[(long)16 * U * NW + b0] = live ? ((MODE == kGru) ? bsh[q] : bsx[q]) : 0.f;
-    }
-  }
-  __syncthreads();
-  for (int q = tid; q < 2 * NW * U; q += NTH) {
-    const int part = q / (NW * U), rem = q - part * NW * U, gt = rem / U, u = rem - gt * U;
-    float s2 = 0.f;
-    for (int r = 0; r < 16; r++) s2 += bs[(long)part * 16 * U * NW + ((long)r * U + u) * NW + gt];
-    p.bias[(((long)grp * dirs + d) * 2 + part) * NW * H + gt * H + u0 + u] = s2;
-  }
-  if (p.cmax) {  // column maxima over all frames (this group's rows, through LDS; max over groups)
-    constexpr int NP = MODE == kGru ? 2 : 1;
-    __syncthreads();
-    if (has_e) {
-#pragma unroll
-      for (int q = 0; q < NW; q++) {
-        bs[((long)en * U + eu) * NW + q] = cmx[q];
-        if (MODE == kGru) bs[(long)16 * U * NW + ((long)en * U + eu) * NW + q] = cme[q];
-      }
-    }
-    __syncthreads();
-    for (int q = tid; q < NP * NW * U; q += NTH) {
-      const int part = q / (NW * U), rem = q - part * NW * U, gt = rem / U, u = rem - gt * U;
-      float m2 = 0.f;
-      for (int r = 0; r < 16; r++) m2 = fmaxf(m2, bs[(long)part * 16 * U * NW + ((long)r * U + u) * NW + gt]);
-      unsigned *dst = p.cmax + (long)part * dirs * NW * H + (long)d * NW * H + gt * H + u0 + u;
-      if (p.rg > 1) atomicMax(dst, __float_as_uint(m2));  // non-negative floats order as their bits
-      else *dst = __float_as_uint(m2);
-    }
-  }
-  if (bad && tid == 0) atomicOr(p.err, 1u);
-}
-
-// ---------------------------------------------------------------------------
-// v6 forward: split-fp16 MFMA over an fp16 hi/lo all-gather of h
-// ---------------------------------------------------------------------------
-// WG (dir, g) owns units u0..u0+U-1; per step it multiplies h_{t-1} [16 x H]
-// by its R slice (the nW*U gate rows of its units) on
-// v_mfma_f32_16x16x32_f16 with the split-fp16 products of the v6 backward
-// (R scaled per WG, h scaled by 2^14: |h| <= 1 for LSTM / GRU), K split over
-// the 4 waves and reduced through LDS in a fixed order, then does the cell
-// update of its (n, unit) elements and publishes h_t as the fp16 hi/lo pair
-// of its units.  The exchange image of a step is A-fragment-major:
-// [dir][kb = k/32][hi|lo][16 rows][32 k] halves (1 KB per fragment), the same
-// 64 KB per step as the fp32 image of v4; a consumer lane loads 16 B of hi
-// and 16 B of lo per 32-k block.  The R slice lives in registers (B
-// fragments) for the whole launch.  Hand-off as v4 (sc1 stores, vmcnt(0),
-// barrier, sc1 epoch flag; sc1 loads).
-// Generalised like rnn_bwd_rec6: row groups of 16 sequences (block b ->
-// direction b % dirs, workgroup (b / dirs) % NWG, group b / (dirs NWG); each
-// group has its own flag lines and step images), NTH = 256 or 512 threads (K
-// split over NTH / 64 waves), U up to 32; P = kPrecBf16 exchanges h as bf16
-// and multiplies by a bf16 R slice (one MFMA per block, no scaling).
-template <int MODE, int U, int H, int NTH, int P>
-__global__ __launch_bounds__(NTH, 1) void rnn_fwd_rec6(RecParams p) {
-  REC_TRACE_INIT;
-  constexpr int NW = MODE == kLstm ? 4 : 3;
-  constexpr int NWV = NTH / 64;
-  // P & 4: IO waves.  The upper half of the waves neither waits for the
-  // hand-off nor multiplies: they load the input projection rows (G) of the
-  // coming steps and pass them through LDS.  A wave's vmcnt counts its loads
-  // and stores in order, so a G load (HBM latency) issued by a hand-off wave
-  // held up that wave's next flag poll / hand-off loads / publish drain
-  // (measured: forward 2.38 -> 1.89 us/step with the G loads left out)
-  constexpr bool IOW = (P & 4) != 0;
-  // the row-major outputs through the IO waves too: measured slower (forward
-  // 2.46 -> 2.52 us/step; the IO waves' waits then delay the post-cell barrier)
-  constexpr bool IO_OUT = false;
-  constexpr int PR = P & 3;
-  constexpr int CW = IOW ? NWV / 2 : NWV;  // hand-off (compute) waves
-  constexpr int NC = NW * U, CT = (NC + 15) / 16, RP = CT * 16 + 1;  // red row pitch (floats)
-  constexpr int KB = H / 32, KBW = (KB + CW - 1) / CW, NWG = H / U;
-  constexpr int CH = U / 8;  // 16-B chunks of a published row part
-  constexpr bool BF = PR == kPrecBf16;
-  constexpr bool STK = PR == kPrecX3S;  // hi / lo stacked in one 16-row A operand (groups of <= 8 rows)
-  constexpr int NP = BF ? 1 : 2;  // parts of an exchanged h: hi (+ lo)
-  // element rows: a stacked group has at most 8, and the folded K partials of
-  // a wave are 8 rows (no thread, no LDS row for the rows that cannot be live)
-  constexpr int ER = STK ? 8 : 16;
-  static_assert(16 * U <= NTH, "one (row, unit) element per thread");
-  static_assert(!IOW || (16 * U == CW * 64 && NW <= 4 && NP * 16 * U / 8 <= 64),
-                "IO waves: the elements fill the compute waves, one publishing wave");
-  using AT = typename std::conditional<BF, __bf16, _Float16>::type;
-  using AV = typename std::conditional<BF, bf16x8, halfx8>::type;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds, loc_lds;
-  __shared__ float wmax[NWV];
-  const int dirs = p.dirs;
-  // xpd = 1: XCD-slot mapping as rnn_bwd_rec6 (block b -> (row group, direction)
-  // slot b & 7, workgroup b >> 3: one XCD per slot under round-robin dispatch)
-  const int d = p.xpd ? (blockIdx.x & 7) % dirs : blockIdx.x % dirs;
-  const int g = p.xpd ? (blockIdx.x >> 3) : (blockIdx.x / dirs) % NWG;
-  const int grp = p.xpd ? (blockIdx.x & 7) / dirs : blockIdx.x / (dirs * NWG);
-  if (g >= NWG || grp >= p.rg) return;
-  const int N = p.N, T = p.T, n0 = grp * p.gs, nend = min(N, n0 + p.gs);
-  const int u0 = g * U;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
-  const long ldy = (long)dirs * H, ldg = (long)dirs * NW * H;
-  constexpr long XG = 2L * KB * NP * 16 * 32;  // halves per row group's image of a step (dirs <= 2)
-  const long XS = XG * p.rg;                    // halves per step image
-  float *red = smem;                                                       // [NWV][16][RP]
-  // [NP][16][U], 16-B aligned.  Offset arithmetic on smem only: a pointer
-  // rounded through an integer loses the LDS address space, and the staging
-  // reads and writes became FLAT instructions (counted in vmcnt, so the
-  // publish waited for every store of the step still in flight)
-  constexpr int RPR = (U % 16 == 0 && NW <= 4 && 4 * U > RP) ? 4 * U : RP;  // red floats per (wave, row)
-  constexpr int kStgOff = (NWV * 16 * RPR + 3 + 3) / 4 * 4;
-  // (stacked: [CW][8][U] float4, the first half of these floats)
-  static_assert(!STK || (U % 16 == 0 && NW <= 4), "stacked: float4 K partials");
-  AT *stg = reinterpret_cast<AT *>(smem + kStgOff);
-  // IO waves: the G rows of step k in slot k & 7, [8][NW][16 U] floats,
-  // filled by LDS-DMA p.gla (3 or 7) steps ahead
-  float *ginl = smem + kStgOff + (NP * 16 * U + 7) / 8 * 4;  // 16-B aligned
-  float *outl = ginl + 8 * NW * 16 * U;  // (IO_OUT) [2][NW + 2][16 U]
-  const float *Wd = p.w + d * p.pl_stride;
-  const float *R = Wd + p.r_off;
-  AT *xch = reinterpret_cast<AT *>(p.xch);
-  if (tid == 0) bad_lds = 0;
-  // ---- R slice -> B fragments: B[k][c] = R[q*H + u0 + u][k], c = q*U + u ----
-  auto rrow = [&](int c) -> const float * {
-    const int q = c / U, u = c - q * U;
-    return R + (long)(q * H + u0 + u) * H;
-  };
-  int sB = 0, sOut = 0;
-  if constexpr (!BF) {
-    float mx = 0.f;
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) {
-      const int c = ct * 16 + fr;
-      if (c < NC) {
-        const float *rr = rrow(c);
-#pragma unroll
-        for (int i = 0; i < KBW; i++) {
-          const int kb = (!IOW || w < CW) ? w + CW * i : KB;
-          if (kb < KB) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) mx = fmaxf(mx, fabsf(rr[kb * 32 + fq * 8 + j]));
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if (lane == 0) wmax[w] = mx;
-    __syncthreads();
-    float m4 = wmax[0];
-#pragma unroll
-    for (int i = 1; i < NWV; i++) m4 = fmaxf(m4, wmax[i]);
-    sB = split_exp(m4);
-    sOut = -(sB + 14);
-  }
-  AV bhi[CT][KBW], blo[BF ? 1 : CT][BF ? 1 : KBW];
-#pragma unroll
-  for (int ct = 0; ct < CT; ct++) {
-    const int c = ct * 16 + fr;
-#pragma unroll
-    for (int i = 0; i < KBW; i++) {
-      const int kb = (!IOW || w < CW) ? w + CW * i : KB;
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        const float v = (c < NC && kb < KB) ? rrow(c)[kb * 32 + fq * 8 + j] : 0.f;
-        if constexpr (BF) {
-          bhi[ct][i][j] = (__bf16)v;
-        } else {
-          _Float16 h, l;
-          split16(ldexpf(v, sB), h, l);
-          bhi[ct][i][j] = h;
-          blo[ct][i][j] = l;
-        }
-      }
-    }
-  }
-  // ---- per-element state: thread tid <-> (row n0 + en, unit u0 + eu) ----
-  const bool has_e = tid < ER * U;
-  const int en = tid / U, eu = tid - en * U;
-  const int n = n0 + en;
-  const bool live = has_e && n < nend;
-  float cst = 0.f, hpv = 0.f, cnew = 0.f, hval = 0.f;
-  float gin[NW], gnx[NW], bR[NW], act[NW];
-#pragma unroll
-  for (int q = 0; q < NW; q++) {
-    gin[q] = gnx[q] = act[q] = 0.f;
-    bR[q] = (MODE == kGru && has_e) ? Wd[p.bR_off + q * H + u0 + eu] : 0.f;
-  }
-  // Row-major addressing of the step loop: the element's byte offsets in a
-  // step's y / aux and G rows stay in two VGPRs (opaque to the compiler, or it
-  // works them out again every step), and the step's rows are wave-uniform
-  // bases (yrow, grow, arow below) moved by one step image a step with scalar
-  // adds -- no per-lane 64-bit index arithmetic between the last MFMA and the
-  // K-partial writes the workgroup's barrier waits for
-  typedef const float __attribute__((address_space(1))) *gcfp;
-  typedef float __attribute__((address_space(1))) *gfp;
-  unsigned yob = (unsigned)(((long)n * ldy + (long)d * H + u0 + eu) * sizeof(float));
-  unsigned gob = (unsigned)(((long)n * ldg + (long)d * NW * H + u0 + eu) * sizeof(float));
-  asm volatile("" : "+v"(yob), "+v"(gob));
-  auto at = [](const float *base, unsigned ob) {  // element at byte offset ob of a step's rows
-    return (gfp) reinterpret_cast<float *>(reinterpret_cast<uintptr_t>(base) + ob);
-  };
-  auto gin_load = [&](const float *gr, float (&dst)[NW]) {  // gr: the step's G rows
-    if (!live) return;
-    const gcfp s = at(gr, gob);
-#pragma unroll
-    for (int q = 0; q < NW; q++) dst[q] = s[q * H];
-  };
-  // bf16_io: the step's h (stg, bf16 [16][U]) as packed rows and columns
-  auto y_pk_store = [&](int tt) {
-    if constexpr (BF) {
-      constexpr int RCH = U / 8;
-      const long f0 = (long)tt * N + n0;
-      const int i = tid;
-      if (i < 16 * RCH) {
-        const int rn = i / RCH, ch = i - rn * RCH;
-        if (n0 + rn < nend)
-          *reinterpret_cast<u32x4 *>(p.yr + (f0 + rn) * ldy + (long)d * H + u0 + ch * 8) =
-              *reinterpret_cast<const u32x4 *>(stg + rn * U + ch * 8);
-      } else if (i < 16 * RCH + 2 * U) {
-        const int col = (i - 16 * RCH) >> 1, half = (i - 16 * RCH) & 1, r0 = half * 8;
-        __bf16 *dst = p.yc + ((long)d * H + u0 + col) * p.kbt64 + f0 + r0;
-        if ((N % 8 == 0) && (n0 % 8 == 0) && n0 + r0 + 8 <= nend) {
-          bf16x8 v;
-#pragma unroll
-          for (int j = 0; j < 8; j++) v[j] = stg[(r0 + j) * U + col];
-          *reinterpret_cast<bf16x8 *>(dst) = v;
-        } else {
-          for (int j = 0; j < 8; j++)
-            if (n0 + r0 + j < nend) dst[j] = stg[(r0 + j) * U + col];
-        }
-      }
-    }
-  };
-  // row-major y, activations (in place of G), aux of a step, given its rows
-  auto out_store = [&](const float *yr, const float *gr, const float *ar) {
-    if (!live) return;
-    if (p.ysc1) __hip_atomic_store(at(yr, yob), hval, __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);  // read by other XCDs during this kernel
-    else *at(yr, yob) = hval;
-    const gfp gd = at(gr, gob);
-#pragma unroll
-    for (int q = 0; q < NW; q++) gd[q * H] = act[q];
-    *at(ar, yob) = cnew;
-  };
-  // IO waves: thread tid - 64 CW <-> element (ion, iou); G of step k into
-  // ginl[k & 1] before step k's K-reduction barrier
-  const int iot = tid - 64 * CW, ion = iot / U, iou = iot - ion * U;
-  const bool io_live = IOW && w >= CW && n0 + ion < nend;
-  // G row of forward-order step kk of this lane's element into slot kk & 7
-  // by LDS-DMA (lane l of IO wave v writes element 64 v + l); NW DMAs per
-  // call whatever kk, so that the waits can count them (rows past N and
-  // steps past T read a valid row and are never used)
-  auto io_dma = [&](int kk) {
-    const int tt = d == 0 ? min(kk, T - 1) : max(T - 1 - kk, 0);
-    const long gr = ((long)tt * N + n0 + (io_live ? ion : 0)) * ldg + (long)d * NW * H + u0 + iou;
-#pragma unroll
-    for (int q = 0; q < NW; q++) {
-      const unsigned dst = __builtin_amdgcn_readfirstlane(
-          (unsigned)reinterpret_cast<uintptr_t>(ginl + ((kk & 7) * NW + q) * 16 * U + (w - CW) * 64));
-      dma_lds_dword(p.G + gr + q * H, dst);
-    }
-  };
-  auto io_out = [&](int kk) {  // row-major outputs of step kk from outl[kk & 1]
-    if (!io_live) return;
-    const int tt = d == 0 ? kk : T - 1 - kk;
-    const float *o = outl + (long)(kk & 1) * (NW + 2) * 16 * U + iot;
-    const long yrow = ((long)tt * N + n0 + ion) * ldy + (long)d * H + u0 + iou;
-    const long grow = ((long)tt * N + n0 + ion) * ldg + (long)d * NW * H + u0 + iou;
-    p.y[yrow] = o[0];
-#pragma unroll
-    for (int q = 0; q < NW; q++) p.G[grow + q * H] = o[(1 + q) * 16 * U];
-    p.aux[yrow] = o[(NW + 1) * 16 * U];
-  };
-  // the IO waves' wait for step k + 1's G: at most (gla - 1) * NW DMAs (the
-  // steps after it) still in flight
-  const bool gla7 = p.gla == 7;
-  auto io_wait = [&]() {
-    if (gla7) {
-      if constexpr (NW == 4) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-    } else {
-      if constexpr (NW == 4) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    }
-  };
-  if constexpr (IOW) {
-    if (w >= CW) {  // steps 0 .. gla - 1; step 0's in place before the loop's first barrier
-      for (int kk = 0; kk < (gla7 ? 7 : 3); kk++) io_dma(kk);
-      io_wait();
-    }
-    __syncthreads();
-  }
-  // the rows of the loop's current step (time t): wave-uniform, one step
-  // image (tstep frames) on at the end of every step
-  const long ysl = (d == 0 ? 1 : -1) * (long)N * ldy, gsl = (d == 0 ? 1 : -1) * (long)N * ldg;
-  const float *yrow = p.y + (long)(d == 0 ? 0 : T - 1) * N * ldy;
-  const float *arow = p.aux + (long)(d == 0 ? 0 : T - 1) * N * ldy;
-  const float *grow = p.G + (long)(d == 0 ? 0 : T - 1) * N * ldg;
-  if constexpr (!IOW) gin_load(grow, gin);
-  int bad = 0;
-  unsigned *myflag = flag6(p, grp, d, g, NWG);
-  // XCD-pinned (p.xpd): the hand-off goes through a ring of p.ring step images
-  // after the T per-step images, kept in the XCD's L2 (plain stores, workgroup-
-  // scope flags) when probe6 finds the direction's workgroups on one XCD; a
-  // streamed projection on the other XCDs reads the per-step images, written
-  // through (sc1) behind the next step's hand-off loads, and follows sc1
-  // copies of the epochs 256 lines on: gflag = k in step k's load phase
-  // (step k - 1's signal drained step k - 2's copy), T + 1 at exit -- "epoch
-  // - 2 = last step out" as the unpinned flags
-  // (aggregated over the direction's workgroups by workgroup 0, as in
-  // rnn_bwd_rec6: agg_flag6 = k after the K-reduction barrier of step k, by
-  // which every producer's signal of step k - 1 drained its copy of step k - 2)
-  // (compiled into the IO-wave variant only, the one chain_ok lets stream
-  // off a pinned producer: the dead code of it in the other variants changed
-  // their schedules -- U = 32 forward 3.19 -> 4.0 us/step at configs[2])
-  const bool fcopy = IOW && p.xpd && p.fcopy;
-  // y rows streamed (p.ysc1): step m's y goes out in step m + 1, behind that
-  // step's hand-off loads, so it has landed once the workgroup publishes step
-  // m + 2; workgroup 0 has every producer's step k - 1 image in step k, so
-  // gflag = k there means rows of steps <= k - 3 are out ("epoch s + 3" as
-  // the backward's rows), T + 2 at exit
-  unsigned *gflag = ((fcopy || p.ysc1) && g == 0) ? agg_flag6(p, grp, d) : nullptr;
-  if (tid == 0) {  // (the side launches' residency gate: beside_recurrence)
-    if (p.xpd) atomicOr(p.flags + kXcdWord, 1u << xcc_id());
-    atomicAdd(p.flags + kResWord, 1u);
-  }
-  if (tid == 0) loc_lds = 0;
-  const int local = (p.xpd && p.allow_local) ? probe6(p, grp, d, g, NWG, bad, &bad_lds, &loc_lds) : 0;
-  if (trc_ && tid == 0) trc_[9] = (unsigned long long)(local + 1);  // step 0, slot 9
-  const long rbase = (long)T * XS;  // ring slots (p.ring > 0)
-  // Self-tagged hand-off (as rnn_bwd_rec6): every fp16 half of step k's h
-  // image carries ((k >> 1) & 1) in its LSB (hi's change is taken up by lo,
-  // lo's own LSB costs 2^-21 of |h| at most); the consumers poll the image
-  // words themselves: no drain, no flag.  Split-fp16 without IO waves, no
-  // write-through copy for a streamed projection, ring of two L2 images set
-  // to tag 1 before the launch.
-  const bool dtag = !BF && !IOW && !fcopy && p.dtag && local && p.ring == 2;
-  // the published 16 B of h: live across the whole loop (used after it), so
-  // that no other value of the step is allocated to the data registers of the
-  // write-through copy still in flight (gfx9 waits for a store's completion
-  // before its data VGPRs are overwritten)
-  u32x4 pv = u32x4{0u, 0u, 0u, 0u};
-  // the per-step images as one loop-invariant buffer (chain_ok: T XS halves < 2 GB)
-  const auto crs = rsrc(xch, fcopy ? (unsigned)(T * XS * sizeof(AT)) : 0u);
-  // publish geometry: store thread s < NP * 16 * CH: part = s / (16 CH), row, chunk
-  const int sp = tid / (16 * CH), sn = (tid / CH) % 16, sch = tid % CH;
-  const int kb0 = u0 >> 5, koff = (u0 & 31) + sch * 8;
-  // rows past N (a group of fewer than 16 sequences) are neither loaded nor stored
-  // (STK: lanes fr >= 8 load the lo part of row fr - 8)
-  const bool arow_live = n0 + (STK ? (fr & 7) : fr) < nend;
-  // per-wave wait: the producers of the k blocks this wave loads (32 / U per block)
-  int wprod = -1;
-  {
-    constexpr int PPK = 32 / U;
-    const int i = lane / PPK, kb = (!IOW || w < CW) ? w + CW * i : KB;
-    if (i < KBW && kb < KB) wprod = kb * PPK + lane % PPK;
-  }
-  const long gimg = (long)grp * XG;
-  const bool pub = tid < NP * 16 * CH && n0 + sn < nend;  // a publishing thread: 16 B of h
-  const long po = gimg + ((((long)d * KB + kb0) * NP + sp) * 16 + sn) * 32 + koff;
-  // stacked fold: the two rows of a tile this lane keeps (row, row + 1)
-  const int frow = (fq & 1) * 4 + (fq >> 1) * 2;
-  int t_prev = -1;
-  for (int k = 0; k < T && !bad; k++) {
-    const int t = d == 0 ? k : T - 1 - k, tp = d == 0 ? t - 1 : t + 1;
-    floatx4 acc[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) acc[ct] = floatx4{0.f, 0.f, 0.f, 0.f};
-    REC_TRACE(k, 0);
-    if (k > 0 && (!IOW || w < CW)) {
-      if (dtag) {
-        // self-tagged: the poll below is the wait
-      } else {
-        if (!wave_wait_prod(flag6(p, grp, d, 0, NWG), wprod, (unsigned)(k + 1), p.err, &bad_lds, p.poll_sleep)) bad = 1;
-      }
-      REC_TRACE(k, 1);
-      const auto rs = rsrc(xch + (p.ring ? rbase + (long)((k - 1) & 1) * XS : (long)tp * XS),
-                           (unsigned)(XS * sizeof(AT)));
-      u32x4 ah[KBW], al[KBW];
-      unsigned aoff[KBW];
-      // unconditional loads (rows past N and k blocks past KB at an offset
-      // past the buffer: the hardware returns zeros), so that the compiler
-      // counts them exactly and the first MFMAs wait for their own loads only
-#pragma unroll
-      for (int i = 0; i < KBW; i++) {
-        const int kb = w + CW * i;
-        const long o = STK ? gimg + ((((long)d * KB + kb) * NP + (fr >> 3)) * 16 + (fr & 7)) * 32 + fq * 8
-                           : gimg + ((((long)d * KB + kb) * NP) * 16 + fr) * 32 + fq * 8;
-        const unsigned off = (kb < KB && arow_live) ? (unsigned)(o * sizeof(AT)) : 0x7fff0000u;
-        aoff[i] = off;
-        ah[i] = ld_sc1(rs, off);
-        if constexpr (!BF && !STK) al[i] = ld_sc1(rs, off + 16 * 32 * sizeof(AT));
-      }
-      if constexpr (!BF) {
-        if (dtag) {
-          // every half of step k - 1 carries ((k - 1) >> 1) & 1 in its LSB
-          // (bits 0 and 16 of a word; 4-B words are single-copy atomic); a
-          // chunk still holding step k - 3's halves is loaded again
-          const unsigned want = ((unsigned)((k - 1) >> 1) & 1u) * 0x00010001u;
-          // (rows past N and k blocks past KB: zeros from past the buffer, no tag)
-          const bool any_live = arow_live && w < KB;
-          auto ready = [&]() {
-            unsigned bad4 = 0u;
-#pragma unroll
-            for (int i = 0; i < KBW; i++) {
-              if (w + CW * i < KB) {
-                bad4 |= (ah[i][0] ^ want) | (ah[i][1] ^ want) | (ah[i][2] ^ want) | (ah[i][3] ^ want);
-                if constexpr (!STK) bad4 |= (al[i][0] ^ want) | (al[i][1] ^ want) | (al[i][2] ^ want) | (al[i][3] ^ want);
-              }
-            }
-            return !any_live || (bad4 & 0x00010001u) == 0u;
-          };
-          int spins = 0;
-          while (!__all(ready())) {  // (not all there yet: the wave loads all its chunks again)
-            if (++spins > kSpinLimit ||
-                ((spins & 255) == 0 &&
-                 __builtin_amdgcn_readfirstlane(__hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))) {
-              bad = 1;
-              if (lane == 0) bad_lds = 1;
-              break;
-            }
-            if (p.poll_sleep) __builtin_amdgcn_s_sleep(1);
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < KBW; i++) {
-              ah[i] = ld_sc1(rs, aoff[i]);
-              if constexpr (!BF && !STK) al[i] = ld_sc1(rs, aoff[i] + 16 * 32 * sizeof(AT));
-            }
-          }
-        }
-      }
-      // all hand-off loads in flight before the first MFMA waits: without
-      // this the scheduler (U = 32) issued the second k block's loads only
-      // after the first block's MFMAs, one more L2 round trip per step
-      __builtin_amdgcn_sched_barrier(0);
-      // the streamed projection's write-through copy of the previous step's
-      // image (pv still holds it), issued behind this step's hand-off loads:
-      // gfx9 counts stores and loads in one vmcnt, so a write-through store
-      // in flight at the next flag poll would hold up that poll; here the
-      // waits for the loads ahead of it do not cover it, and this step's
-      // signal drains it (the next step publishes its epoch)
-      // (every lane of every wave issues it -- non-publishing lanes at an
-      // offset past the buffer, which the hardware drops -- so that no
-      // branch makes the compiler's wait counts conservative)
-      // (unconditional: without a consumer crs covers 0 bytes and the store is dropped)
-      __builtin_amdgcn_raw_buffer_store_b128(pv, crs, pub ? (int)(po * sizeof(AT)) : 0x7ffffff0,
-                                             fcopy ? (int)(tp * XS * sizeof(AT)) : 0, 16);
-
-#pragma unroll
-      for (int i = 0; i < KBW; i++) {
-        if (w + CW * i < KB) {
-          const AV a0 = __builtin_bit_cast(AV, ah[i]);
-          if constexpr (BF) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bhi[ct][i], acc[ct], 0, 0, 0);
-          } else if constexpr (STK) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, bhi[ct][i], acc[ct], 0, 0, 0);
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, blo[ct][i], acc[ct], 0, 0, 0);
-          } else {
-            const AV a1 = __builtin_bit_cast(AV, al[i]);
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, bhi[ct][i], acc[ct], 0, 0, 0);
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, blo[ct][i], acc[ct], 0, 0, 0);
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, bhi[ct][i], acc[ct], 0, 0, 0);
-          }
-        }
-      }
-      if constexpr (!IOW) {
-        // this step's input projection row (loaded behind the last step's
-        // hand-off loads) moves in here: the first MFMA's wait for the
-        // hand-off loads has retired those older loads too (one in-order
-        // vmcnt), so the cell below does not wait for memory.  Rotated in
-        // the cell instead, the wait for them -- HBM misses -- and for the
-        // row stores issued with them stood between the cell's exp and rcp
-#pragma unroll
-        for (int q = 0; q < NW; q++) gin[q] = gnx[q];
-      }
-    }
-    asm volatile("" ::: "memory");
-    // behind the hand-off loads: last step's row-major outputs, next step's input projection
-    if (!IO_OUT && t_prev >= 0) out_store(yrow - ysl, grow - gsl, arow - ysl);
-    // (stg still holds step t_prev's h: the cell phase below rewrites it)
-    if (BF && p.yr && t_prev >= 0) y_pk_store(t_prev);
-    if (!IOW && k + 1 < T) gin_load(grow + gsl, gnx);
-    // K partials through LDS.  U % 16 == 0: column ct * 16 + fr of the
-    // tile is gate ct / (U / 16) of unit (ct % (U / 16)) * 16 + fr, so a lane
-    // holds every gate of its (row, unit) elements: one float4 per (wave,
-    // row, unit) [NWV][16][U][4], and a cell thread sums NWV float4 reads
-    // (4x fewer LDS instructions than one float per gate)
-    constexpr bool RED4 = U % 16 == 0 && NW <= 4;
-    if constexpr (STK) {
-      // Rows 8..15 of a tile (lanes 32..63) hold the lo parts' products of rows
-      // 0..7: row r + row r + 8, hi first.  v_permlane32_swap of register i
-      // against register i + 2 (not against itself): one swap serves two rows,
-      // every lane ends with two live sums: lanes 0..31 rows fq * 4 + {0, 1},
-      // lanes 32..63 rows (fq - 2) * 4 + {2, 3}  (= frow, frow + 1).  Half the
-      // swaps, no garbage lanes, and a wave's partials are 8 rows of float4
-      constexpr int SU = U / 16;
-      float sm2[CT][2];
-#pragma unroll
-      for (int ct = 0; ct < CT; ct++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[ct][j]), __float_as_uint(acc[ct][j + 2]),
-                                                          false, false);
-          sm2[ct][j] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        }
-#pragma unroll
-      for (int su = 0; su < SU; su++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-          floatx4 v4 = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int q = 0; q < NW; q++) v4[q] = sm2[q * SU + su][j];
-          st4(red + (((long)(w * ER + frow + j) * U + su * 16 + fr) << 2), v4);
-        }
-    } else if constexpr (RED4) {
-      constexpr int SU = U / 16;
-      if (!IOW || w < CW) {
-#pragma unroll
-        for (int su = 0; su < SU; su++)
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            floatx4 v4 = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < NW; q++) v4[q] = acc[q * SU + su][i];
-            st4(red + (((long)(w * 16 + fq * 4 + i) * U + su * 16 + fr) << 2), v4);
-          }
-      }
-    } else {
-#pragma unroll
-      for (int ct = 0; ct < CT; ct++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) red[(w * 16 + fq * 4 + i) * RP + ct * 16 + fr] = acc[ct][i];
-    }
-    lds_barrier<IOW>();
-    if (bad_lds) bad = 1;
-    // the aggregated epoch (before the signal: a write-through flag store
-    // left in flight there would hold up the next step's first flag poll)
-    if (gflag && k > 0 && tid == 0) __hip_atomic_store(gflag, (unsigned)k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    REC_TRACE(k, 3);
-    if (has_e) {
-      float rh[NW];
-      if constexpr (RED4) {
-        floatx4 sm = *reinterpret_cast<const floatx4 *>(red + (((long)en * U + eu) << 2));  // fixed order
-#pragma unroll
-        for (int v = 1; v < CW; v++) sm += *reinterpret_cast<const floatx4 *>(red + (((long)(v * ER + en) * U + eu) << 2));
-        if constexpr (IOW) {  // this step's G row, put there by the IO waves
-#pragma unroll
-          for (int q = 0; q < NW; q++) gin[q] = ginl[((k & 7) * NW + q) * 16 * U + tid];
-        }
-#pragma unroll
-        for (int q = 0; q < NW; q++) rh[q] = BF ? sm[q] : ldexpf(sm[q], sOut);
-      } else {
-#pragma unroll
-        for (int q = 0; q < NW; q++) {
-          const int c = q * U + eu;
-          float sm = red[(0 * 16 + en) * RP + c];  // the waves' K partials in a fixed order
-#pragma unroll
-          for (int v = 1; v < NWV; v++) sm += red[(v * 16 + en) * RP + c];
-          rh[q] = BF ? sm : ldexpf(sm, sOut);
-        }
-      }
-      float h;
-      if (MODE == kLstm) {
-        act[0] = fsigm(gin[0] + rh[0]);
-        act[1] = fsigm(gin[1] + rh[1]);
-        act[2] = ftanh(gin[2] + rh[2]);
-        act[3] = fsigm(gin[3] + rh[3]);
-        cst = act[1] * cst + act[0] * act[2];
-        cnew = cst;
-        h = act[3] * ftanh(cst);
-      } else {
-        act[0] = fsigm(gin[0] + rh[0] + bR[0]);
-        act[1] = fsigm(gin[1] + rh[1] + bR[1]);
-        cnew = rh[2] + bR[2];
-        act[2] = ftanh(gin[2] + act[0] * cnew);
-        h = (1.f - act[1]) * act[2] + act[1] * hpv;
-        hpv = h;
-      }
-      if (!live) h = 0.f;
-      hval = h;
-      if constexpr (IO_OUT) {  // outputs for the IO waves (stored during the next step)
-        float *o = outl + (long)(k & 1) * (NW + 2) * 16 * U + tid;
-        o[0] = h;
-#pragma unroll
-        for (int q = 0; q < NW; q++) o[(1 + q) * 16 * U] = act[q];
-        o[(NW + 1) * 16 * U] = cnew;
-      }
-
-      if constexpr (BF) {
-        stg[en * U + eu] = (__bf16)h;
-      } else {
-        _Float16 hh, hl;
-        if (!IOW) {  // hi's LSB := tag, lo takes up the change, then lo's LSB := tag
-          // (in every mode a self-tagged launch may take: pinned and unpinned
-          // runs stay bit-identical)
-          const unsigned short tgh = (unsigned short)((k >> 1) & 1);
-          const float x = h * 16384.f;
-          hh = __builtin_bit_cast(_Float16, (unsigned short)((__builtin_bit_cast(unsigned short, (_Float16)x) & 0xFFFEu) | tgh));
-          hl = __builtin_bit_cast(_Float16, (unsigned short)((__builtin_bit_cast(unsigned short, (_Float16)(x - (float)hh)) & 0xFFFEu) | tgh));
-        } else {
-          split16(h * 16384.f, hh, hl);
-        }
-        stg[en * U + eu] = hh;
-        stg[(16 + en) * U + eu] = hl;
-      }
-    }
-    if (IOW && w >= CW) {
-      // IO waves, while the cell threads work: step k + 1's G (loaded during
-      // step k - 1) into its slot -- read by the cell threads after the next
-      // K-reduction barrier; the slot's step k - 1 readers passed the
-      // barrier below last step -- then step k + 2's loads, then the
-      // row-major outputs of step k - 1 (written before the last barrier;
-      // their slot is rewritten after the next K-reduction barrier)
-      {
-        // step k + gla's G into slot (k + gla) & 7 (gla <= 7: last read by the
-        // cell threads of step k - 1 at the latest, before the last barrier),
-        // then wait for step k + 1's: in place before the barrier below,
-        // gla - 1 steps after it was asked for
-        io_dma(k + (gla7 ? 7 : 3));
-        io_wait();
-      }
-      if (IO_OUT && k > 0) io_out(k - 1);
-    }
-    lds_barrier<IOW>();
-    if (pub) {
-      pv = *reinterpret_cast<const u32x4 *>(stg + (sp * 16 + sn) * U + sch * 8);
-      const auto ro = rsrc(xch + (p.ring ? rbase + (long)(k & 1) * XS : (long)t * XS), (unsigned)(XS * sizeof(AT)));
-      // local: plain stores stay in the XCD's L2 for the consumers' sc1 loads
-      if (local) __builtin_amdgcn_raw_buffer_store_b128(pv, ro, (int)(po * sizeof(AT)), 0, 0);
-      else __builtin_amdgcn_raw_buffer_store_b128(pv, ro, (int)(po * sizeof(AT)), 0, 16);
-    }
-    REC_TRACE(k, 7);
-    if constexpr (NP * 16 * CH <= 64) {
-      // one publishing wave (wave 0 stores the whole h part): it drains its
-      // own stores and raises the flag, no workgroup barrier.  The other
-      // waves go on to the next step's wait: their reads of red and stg this
-      // step all came before the barrier above, and the next writes of either
-      // follow the next K-reduction barrier, which wave 0 reaches only after
-      // its stg read
-      if (w == 0 && !dtag) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) {
-          if (local) __hip_atomic_store(myflag, (unsigned)(k + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          else __hip_atomic_store(myflag, (unsigned)(k + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-    } else if (!dtag) {
-      signal_epoch(myflag, (unsigned)(k + 2), local);
-    }
-    REC_TRACE(k, 4);
-    t_prev = t;
-    yrow += ysl; arow += ysl; grow += gsl;
-    REC_TRACE(k, 5);
-  }
-  if (IOW && w >= CW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the IO waves' DMAs (ahead of T) land
-  if (t_prev >= 0 && !bad) {
-    if (BF && p.yr) y_pk_store(t_prev);
-    if constexpr (IO_OUT) {
-      if (w >= CW) io_out(T - 1);  // outl of the last step: written before the loop's last barrier
-    } else {
-      out_store(yrow - ysl, grow - gsl, arow - ysl);
-    }
-  }
-  if ((fcopy || p.ysc1) && !bad) {  // the last step's copy / rows, then (workgroup 0) every producer's, then the epoch
-    if (fcopy && pub)
-      __builtin_amdgcn_raw_buffer_store_b128(pv, rsrc(xch + (long)t_prev * XS, (unsigned)(XS * sizeof(AT))),
-                                             (int)(po * sizeof(AT)), 0, 16);
-    signal_epoch(myflag, (unsigned)(T + 2), local);
-    if (gflag) {
-      wait_flags6(flag6(p, grp, d, 0, NWG), NWG, (unsigned)(T + 2), p.err, bad, &bad_lds, p.poll_sleep);
-      if (!bad && tid == 0)
-        __hip_atomic_store(gflag, (unsigned)(fcopy ? T + 1 : T + 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  asm volatile("" ::"v"(pv));
-  if (bad && tid == 0) atomicOr(p.err, 1u);
-}
-
-template <typename F>
-static void set_lds(F f, size_t bytes) {
-  static size_t done[8] = {0};
-  (void)done;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
-                      (int)bytes);
-}
-
-template <int MODE, int RT>
-static void launch_one(bool fwd, const RecParams &p, dim3 grid, size_t lds, hipStream_t s, int ver) {
-  if (ver == 4) {
-    if (fwd) {
-      set_lds(rnn_fwd_rec4<MODE, RT>, lds);
-      hipLaunchKernelGGL((rnn_fwd_rec4<MODE, RT>), grid, dim3(NT), lds, s, p);
-    } else {
-      set_lds(rnn_bwd_rec4<MODE, RT>, lds);
-      hipLaunchKernelGGL((rnn_bwd_rec4<MODE, RT>), grid, dim3(NT), lds, s, p);
-    }
-    return;
-  }
-  if (fwd) {
-    set_lds(rnn_fwd_rec<MODE, RT>, lds);
-    hipLaunchKernelGGL((rnn_fwd_rec<MODE, RT>), grid, dim3(NT), lds, s, p);
-  } else {
-    set_lds(rnn_bwd_rec<MODE, RT>, lds);
-    hipLaunchKernelGGL((rnn_bwd_rec<MODE, RT>), grid, dim3(NT), lds, s, p);
-  }
-}
-template <int MODE>
-static void launch_mode(bool fwd, const RecParams &p, dim3 grid, size_t lds, hipStream_t s, int ver) {
-  switch (p.Npad / 16) {
-    case 1: launch_one<MODE, 1>(fwd, p, grid, lds, s, ver); break;
-    case 2: launch_one<MODE, 2>(fwd, p, grid, lds, s, ver); break;
-    case 3: launch_one<MODE, 3>(fwd, p, grid, lds, s, ver); break;
-    default: launch_one<MODE, 4>(fwd, p, grid, lds, s, ver); break;
-  }
-}
-// v6 shapes that compile: H in {256, 320, 512, 1024}; U in {8, 16} at 256
-// threads, U = 32 at 512 threads (H / (16 * waves) output tiles per wave and
-// H / U producers in groups of 512 / (4 U) for the backward)
-template <int U, int H, int NTH>
-constexpr bool v6_shape_ok() {
-  return (NTH == (U == 32 ? 512 : 256) || (U == 16 && (NTH == 512 || NTH == 1024) && H == 512)) && H % (16 * (NTH / 64)) == 0 &&
-         (H / U) % (NTH / (4 * U)) == 0;
-}
-// rec6_scratch_bytes: launch6 with this set names the kernel it would launch
-// (its private segment size lands here) instead of launching it
-thread_local size_t *g_rec6_probe = nullptr;
-static size_t kernel_scratch(const void *f) {
-  hipFuncAttributes a{};
-  KCTC_HIP_CHECK(hipFuncGetAttributes(&a, f));
-  return a.localSizeBytes;
-}
-template <int MODE, int U, int H, int NTH, int P>
-static void launch6_shape(bool fwd, const RecParams &p, dim3 grid, size_t lds, hipStream_t s) {
-  if constexpr (v6_shape_ok<U, H, NTH>()) {
-    if (g_rec6_probe) {
-      if (fwd) *g_rec6_probe = kernel_scratch(reinterpret_cast<const void *>(rnn_fwd_rec6<MODE, U, H, NTH, P>));
-      else if constexpr ((P & 4) == 0)
-        *g_rec6_probe = kernel_scratch(reinterpret_cast<const void *>(rnn_bwd_rec6<MODE, U, H, NTH, P>));
-      return;
-    }
-    if (fwd) {
-      set_lds(rnn_fwd_rec6<MODE, U, H, NTH, P>, lds);
-      hipLaunchKernelGGL((rnn_fwd_rec6<MODE, U, H, NTH, P>), grid, dim3(NTH), lds, s, p);
-    } else if constexpr ((P & 4) == 0) {
-      set_lds(rnn_bwd_rec6<MODE, U, H, NTH, P>, lds);
-      hipLaunchKernelGGL((rnn_bwd_rec6<MODE, U, H, NTH, P>), grid, dim3(NTH), lds, s, p);
-    } else {
-      throw std::logic_error("v6 recurrence: IO waves are a forward variant");
-    }
-  } else {
-    throw std::logic_error("v6 recurrence: shape not compiled");
-  }
-}
-template <int MODE, int U, int NTH, int P>
-static void launch6_h(bool fwd, const RecParams &p, dim3 grid, size_t lds, hipStream_t s) {
-  switch (p.H) {
-    case 256: launch6_shape<MODE, U, 256, NTH, P>(fwd, p, grid, lds, s); break;
-    case 320: launch6_shape<MODE, U, 320, NTH, P>(fwd, p, grid, lds, s); break;
-    case 512: launch6_shape<MODE, U, 512, NTH, P>(fwd, p, grid, lds, s); break;
-    case 1024: launch6_shape<MODE, U, 1024, NTH, P>(fwd, p, grid, lds, s); break;
-    default: throw std::logic_error("v6 recurrence: H not compiled");
-  }
-}
-static int env_int(const char *name, int dflt);
-template <int MODE, int P>
-static void launch6_u(bool fwd, int nth, const RecParams &p, dim3 grid, size_t lds, hipStream_t s) {
-  switch (p.U) {
-    case 8: launch6_h<MODE, 8, 256, P>(fwd, p, grid, lds, s); break;
-    case 16:
-      if (nth == 1024) launch6_h<MODE, 16, 1024, P>(fwd, p, grid, lds, s);
-      else if (nth == 512) {
-        // row groups of <= 8 sequences: hi / lo stacked in one MFMA operand
-        // (all four products: equally accurate or better), on by default in
-        // both directions: the stacked forward (one A load per k block, 2/3
-        // of the MFMAs) runs 1.76 us/step against 2.05 for the IO-wave
-        // forward (round 4); the transposed stacked backward with its DPP row
-        // fold 1.91 against 2.43 (round 5).  KCTC_STK_FWD (forward; KCTC_STK
-        // for both)
-        const int stk = fwd ? env_int("KCTC_STK_FWD", env_int("KCTC_STK", 1)) : env_int("KCTC_STK", 1);
-        if constexpr (P == kPrecX3) {
-          if (p.gs <= 8 && stk) {
-            launch6_h<MODE, 16, 512, kPrecX3S>(fwd, p, grid, lds, s);
-            break;
-          }
-        }
-        // forward with IO waves (the G loads off the hand-off waves)
-        if constexpr (MODE == kLstm || MODE == kGru) {
-          if (fwd) {
-            launch6_h<MODE, 16, 512, P | 4>(fwd, p, grid, lds, s);
-            break;
-          }
-        }
-        launch6_h<MODE, 16, 512, P>(fwd, p, grid, lds, s);
-      } else {
-        launch6_h<MODE, 16, 256, P>(fwd, p, grid, lds, s);
-      }
-      break;
-    default: launch6_h<MODE, 32, 512, P>(fwd, p, grid, lds, s); break;
-  }
-}
-static void launch6(bool fwd, int mode, int prec, int nth, const RecParams &p, dim3 grid, size_t lds,
-                    hipStream_t s) {
-  if (mode == kLstm) {
-    if (prec == kPrecBf16) launch6_u<kLstm, kPrecBf16>(fwd, nth, p, grid, lds, s);
-    else launch6_u<kLstm, kPrecX3>(fwd, nth, p, grid, lds, s);
-  } else {
-    if (prec == kPrecBf16) launch6_u<kGru, kPrecBf16>(fwd, nth, p, grid, lds, s);
-    else launch6_u<kGru, kPrecX3>(fwd, nth, p, grid, lds, s);
-  }
-}
-static void launch_rec(bool fwd, int mode, const RecParams &p, dim3 grid, size_t lds, hipStream_t s,
-                       int ver) {
-  switch (mode) {
-    case kLstm: launch_mode<kLstm>(fwd, p, grid, lds, s, ver); break;
-    case kGru: launch_mode<kGru>(fwd, p, grid, lds, s, ver); break;
-    case kRelu: launch_mode<kRelu>(fwd, p, grid, lds, s, ver); break;
-    default: launch_mode<kTanh>(fwd, p, grid, lds, s, ver); break;
-  }
+// A recurrence kernel (rec6_kernel / rec_generic_kernel) on `nth` threads per workgroup; it was compiled
+// against its own translation unit's copy of RecParams: the layouts agree only through rec_common.h
+static void launch_rec(const void *k, const RecParams &p, dim3 grid, int nth, size_t lds, hipStream_t s) {
+  (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  void *args[] = {const_cast<RecParams *>(&p)};
+  KCTC_HIP_CHECK(hipLaunchKernel(k, grid, dim3(nth), args, lds, s));
 }
 
 // KCTC_REC_TRACE=<dir>: trace the first forward and the first backward
@@ -3247,20 +283,22 @@ struct RecTrace {
   }
 };
 
-static int env_int(const char *name, int dflt) {
-  const char *v = getenv(name);
-  return v ? atoi(v) : dflt;
+static size_t fwd_lds_bytes(const RnnDesc &d, int N, int U) {
+  const int ncol = (d.nw() * U + 15) / 16 * 16, Npad = (N + 15) / 16 * 16;
+  return sizeof(float) * ((size_t)ncol * (d.H + 4) + 4 * (size_t)Npad * ncol);
+}
+static size_t bwd_lds_bytes(const RnnDesc &d, int N, int U, int ver = 3) {
+  const int Npad = (N + 15) / 16 * 16;
+  return sizeof(float) * ((size_t)(ver == 4 ? 16 : U) * (d.nw() * d.H + 4) +
+                          std::max(4 * (size_t)Npad * 16, (size_t)2 * N * U * d.nw()));
 }
 
 // pick U (units per workgroup): divides H, multiple of 4, blocks <= 256
 static int pick_fwd_u(const RnnDesc &d, int N) {
-  const int NW = d.nw();
   auto ok = [&](int U) {
-    if (U < 4 || U % 4 || d.H % U || NW * U > 16 * kMaxCT || N * U / 4 > NT) return false;
+    if (U < 4 || U % 4 || d.H % U || d.nw() * U > 16 * kMaxCT || N * U / 4 > NT) return false;
     if ((long)d.dirs * (d.H / U) > 256) return false;
-    const int ncol = (NW * U + 15) / 16 * 16, Npad = (N + 15) / 16 * 16;
-    const size_t lds = sizeof(float) * ((size_t)ncol * (d.H + 4) + 4 * (size_t)Npad * ncol);
-    return lds <= 160 * 1024;
+    return fwd_lds_bytes(d, N, U) <= 160 * 1024;
   };
   // smallest U that keeps every workgroup resident (<= 256 = one per CU):
   // per-step MFMA latency falls with U (measured: U=4 < 8 < 16 on BLSTM-512)
@@ -3271,16 +309,6 @@ static int pick_fwd_u(const RnnDesc &d, int N) {
 
 // v4 (XCD-local): nwg = H/U <= kCusPerXcd workgroups per direction, one XCD each.
 constexpr int kCusPerXcd = 32;
-static size_t fwd_lds_bytes(const RnnDesc &d, int N, int U) {
-  const int ncol = (d.nw() * U + 15) / 16 * 16, Npad = (N + 15) / 16 * 16;
-  return sizeof(float) * ((size_t)ncol * (d.H + 4) + 4 * (size_t)Npad * ncol);
-}
-static size_t bwd_lds_bytes(const RnnDesc &d, int N, int U, int ver = 3) {
-  const int Npad = (N + 15) / 16 * 16;
-  return sizeof(float) * ((size_t)(ver == 4 ? 16 : U) * (d.nw() * d.H + 4) +
-                          std::max(4 * (size_t)Npad * 16, (size_t)2 * N * U * d.nw()));
-}
-static int rec_version() { return 4; }
 // XCD slots one direction spans for U units per workgroup (0: not a v4 shape)
 static int v4_xpd(const RnnDesc &d, int U) {
   if (U <= 0 || d.H % U) return 0;
@@ -3290,7 +318,7 @@ static int v4_xpd(const RnnDesc &d, int U) {
   return (x == 1 || x == 2 || x == 4 || x == 8) && x * d.dirs <= 8 ? x : 0;
 }
 static int pick_fwd_u4(const RnnDesc &d, int N) {
-  if (rec_version() != 4 || d.dirs > 8) return 0;
+  if (d.dirs > 8) return 0;
   auto ok = [&](int U) {
     return U >= 4 && U % 4 == 0 && v4_xpd(d, U) && d.nw() * U <= 16 * kMaxCT && N * U <= kMaxEPT * NT &&
            fwd_lds_bytes(d, N, U) <= 160 * 1024;
@@ -3302,7 +330,7 @@ static int pick_fwd_u4(const RnnDesc &d, int N) {
   return 0;
 }
 static int pick_bwd_u4(const RnnDesc &d, int N) {
-  if (rec_version() != 4 || d.dirs > 8) return 0;
+  if (d.dirs > 8) return 0;
   auto ok = [&](int U) {
     return U >= 4 && U <= 16 && U % 4 == 0 && v4_xpd(d, U) && N * U <= kMaxEPT * NT &&
            bwd_lds_bytes(d, N, U, 4) <= 160 * 1024;
@@ -3329,17 +357,11 @@ static int pick_bwd_u4(const RnnDesc &d, int N) {
 // knob applies up to N = 32.  pick6
 // falls back to 16 when no workgroup partition fits the groups of 8.
 static int v6_group_rows(int N, bool fwd) {
-  const int dflt = N <= 16 ? 8 : 16;
-  const int want = env_int("KCTC_REC_GS", dflt);
+  const int want = env_int("KCTC_REC_GS", N <= 16 ? 8 : 16);
   return (want == 8 && N > 8 && N <= 32) ? 8 : 16;
 }
-struct V6Cfg {
-  int U = 0, nth = 0, rg = 0, gs = 16;
-  explicit operator bool() const { return U > 0; }
-};
 static V6Cfg pick6(const RnnDesc &d, int N, bool fwd, int gs_force = 0) {
   V6Cfg c;
-  if (rec_version() != 4) return c;
   if ((d.mode != kLstm && d.mode != kGru) || N <= 0 || N > 64 || d.dirs > 2) return c;
   if (d.H != 256 && d.H != 320 && d.H != 512 && d.H != 1024) return c;
   const int gs = gs_force ? gs_force : v6_group_rows(N, fwd), rg = (N + gs - 1) / gs;
@@ -3355,10 +377,21 @@ static V6Cfg pick6(const RnnDesc &d, int N, bool fwd, int gs_force = 0) {
     // U = 16 at H = 512 runs 512 threads (K split over 8 waves; measured on
     // BLSTM-512 N=16: forward 31.9 -> 28.4, backward 34.4 -> 32.9 ms/step of
     // recurrence vs 256 threads; 1024 threads 30.5 / 33.5)
-    const int want_nth = d.H == 512 ? 512 : 256;
-    c.nth = U == 32 ? 512 : (U == 16 && d.H == 512 && (want_nth == 512 || want_nth == 1024)) ? want_nth : 256;
+    c.nth = U == 32 ? 512 : (U == 16 && d.H == 512) ? 512 : 256;
     c.rg = rg;
     c.gs = gs;
+    // The kernel variant, at U = 16 / 512 threads.  Row groups of <= 8
+    // sequences: hi / lo stacked in one MFMA operand (all four products:
+    // equally accurate or better), on by default in both directions: the
+    // stacked forward (one A load per k block, 2/3 of the MFMAs) runs 1.76
+    // us/step against 2.05 for the IO-wave forward (round 4); the transposed
+    // stacked backward with its DPP row fold 1.91 against 2.43 (round 5).
+    // KCTC_STK_FWD (forward; KCTC_STK for both).  Else the forward runs
+    // with IO waves (the G loads off the hand-off waves).
+    const bool wide16 = U == 16 && c.nth == 512;
+    const int stk = fwd ? env_int("KCTC_STK_FWD", env_int("KCTC_STK", 1)) : env_int("KCTC_STK", 1);
+    const bool stacked = wide16 && d.prec != kPrecBf16 && gs <= 8 && stk;
+    c.variant = stacked ? kRec6Stacked : wide16 && fwd ? kRec6IoWave : kRec6Plain;
     return c;
   };
   for (int U : {16, 32, 8})
@@ -3368,14 +401,12 @@ static V6Cfg pick6(const RnnDesc &d, int N, bool fwd, int gs_force = 0) {
     }
   return gs == 8 ? pick6(d, N, fwd, 16) : c;
 }
-static int pick_fwd_u6(const RnnDesc &d, int N) { return pick6(d, N, true).U; }
-static int pick_bwd_u6(const RnnDesc &d, int N) { return pick6(d, N, false).U; }
 
 static size_t fwd6_lds_bytes(const RnnDesc &d, const V6Cfg &c) {
   const int CT = (d.nw() * c.U + 15) / 16, nwv = c.nth / 64, np = d.prec == kPrecBf16 ? 1 : 2;
   const size_t rp = std::max(CT * 16 + 1, 4 * c.U);  // rnn_fwd_rec6's RPR (float4 K partials)
-  // + the IO waves' G (and output) slots, for the shape that runs them (launch6_u)
-  const bool iow = c.U == 16 && c.nth == 512;
+  // + the IO waves' G (and output) slots; the stacked forward's launch keeps them (forward cfg only)
+  const bool iow = c.variant == kRec6IoWave || c.variant == kRec6Stacked;
   const size_t b = sizeof(float) * (nwv * 16 * rp + 8) + np * 16 * (size_t)c.U * 2 + 16 +
                    (iow ? sizeof(float) * 16 * c.U * (8 * d.nw() + 2 * (d.nw() + 2)) + 16 + 4 * 64 * 4 : 0);
   return std::max(b, (size_t)96 * 1024);  // one recurrence workgroup per CU
@@ -3395,7 +426,6 @@ static size_t bwd6_lds_bytes(const RnnDesc &d, const V6Cfg &c) {
 // never reused within a launch (T x dirs x nwg x H x Npad floats, 4.2 GB for
 // BLSTM-512 N=16 T=2000).  Library-owned so that the components of a network
 // share it; launches on one device are ordered through its event.
-namespace {
 struct XchPool {
   void *p = nullptr;
   size_t bytes = 0;
@@ -3403,7 +433,6 @@ struct XchPool {
 };
 std::mutex g_xch_mu;
 XchPool g_xch[64];
-}  // namespace
 
 static float *xch_acquire(size_t bytes, hipStream_t s) {
   int dev = 0;
@@ -3432,14 +461,10 @@ static void xch_release(hipStream_t s) {
 }
 
 static int pick_bwd_u(const RnnDesc &d, int N) {
-  const int K = d.nw() * d.H;
   auto ok = [&](int U) {
     if (U < 4 || U % 4 || U > 16 || d.H % U || N * U / 4 > NT) return false;
     if ((long)d.dirs * (d.H / U) > 256) return false;
-    const int Npad = (N + 15) / 16 * 16;
-    const size_t lds = sizeof(float) * ((size_t)U * (K + 4) + std::max(4 * (size_t)Npad * 16,
-                                                                        (size_t)2 * N * U * d.nw()));
-    return lds <= 160 * 1024;
+    return bwd_lds_bytes(d, N, U) <= 160 * 1024;
   };
   for (int U : {16, 8, 4})
     if (ok(U)) return U;
@@ -3517,24 +542,13 @@ int g_usable_cus = 0, g_comm_cus = 0;
 bool rec6_scratch_free(const RnnDesc &d, int N, bool fwd) {
   const V6Cfg c6 = pick6(d, N, fwd);
   if (!c6) return false;
-  static thread_local std::map<long, bool> memo;
-  const int stk = fwd ? env_int("KCTC_STK_FWD", env_int("KCTC_STK", 1)) : env_int("KCTC_STK", 1);
-  const long key = ((((long)fwd * 4 + d.mode) * 4 + d.prec) * 64 + c6.U) * 2048 * 2048 + (long)c6.nth * 2048 * 2 +
-                   (long)d.H * 2 + (c6.gs <= 8 && stk ? 1 : 0);
-  auto it = memo.find(key);
+  static thread_local std::map<const void *, bool> memo;
+  const void *k = rec6_kernel(fwd, d.mode, d.prec, d.H, c6);
+  auto it = memo.find(k);
   if (it != memo.end()) return it->second;
-  RecParams q{};
-  q.H = d.H; q.U = c6.U; q.gs = c6.gs; q.rg = c6.rg; q.dirs = d.dirs; q.nwg = d.H / c6.U;
-  size_t bytes = 0;
-  g_rec6_probe = &bytes;
-  try {
-    launch6(fwd, d.mode, d.prec, c6.nth, q, dim3(1), 0, nullptr);
-  } catch (...) {
-    g_rec6_probe = nullptr;
-    throw;
-  }
-  g_rec6_probe = nullptr;
-  return memo[key] = bytes == 0;
+  hipFuncAttributes a{};
+  KCTC_HIP_CHECK(hipFuncGetAttributes(&a, k));
+  return memo[k] = a.localSizeBytes == 0;
 }
 
 // XCDs an XCD-pinned v6 recurrence of (d, N) occupies (bit x: XCD x), 0
@@ -3636,14 +650,11 @@ bool chain_ok(const RnnDesc &d, int ver, int T, int N, const RnnFwdChain *c) {
   // than the 256-tile GEMM after it costs (configs[1]: 555.9k vs 564.8k
   // frames/s same box); KCTC_FWD_STREAM_PINNED=1 streams anyway
   if (xcd_mask(d, N, true) && !env_int("KCTC_FWD_STREAM_PINNED", 0)) return false;
-  // and only the IO-wave variant (U = 16, 512 threads) carries the copies
-  // (launch6_u: U = 16 / 512 threads, not the stacked variant)
-  if (xcd_mask(d, N, true) && !(pick6(d, N, true).U == 16 && pick6(d, N, true).nth == 512 &&
-                                !(pick6(d, N, true).gs <= 8 && env_int("KCTC_STK_FWD", env_int("KCTC_STK", 1)))))
-    return false;
+  // and only the IO-wave variant carries the copies (not bf16 in 8-row groups: never run pinned with them)
   const V6Cfg c6 = pick6(d, N, true);
+  if (xcd_mask(d, N, true) && (c6.variant != kRec6IoWave || (d.prec == kPrecBf16 && c6.gs <= 8))) return false;
   if (!c6 || !stream_block_budget(d.dirs * (d.H / c6.U) * c6.rg, false)) return false;
-  const long xs = 2L * (d.H / 32) * (d.prec == kPrecBf16 ? 1 : 2) * 16 * 32 * pick6(d, N, true).rg;  // halves per step image
+  const long xs = 2L * (d.H / 32) * (d.prec == kPrecBf16 ? 1 : 2) * 16 * 32 * c6.rg;  // halves per step image
   if ((long)T * xs * 2 >= (1L << 31)) return false;
   return c->ws_bytes >= rnn_workspace_bytes(n, T, N) &&
          c->res_bytes >= sizeof(float) * (size_t)rnn_reserve_layout(n, T, N).total;
@@ -3800,6 +811,11 @@ int rnn_usable_cus() {
   return g_usable_cus > 0 ? std::min(g_usable_cus, c) : c;
 }
 int rnn_comm_cus() { return g_comm_cus; }
+const void *rnn_rec6_select(const RnnDesc &d, int N, bool fwd, int cfg[5]) {
+  const V6Cfg c = pick6(d, N, fwd);
+  cfg[0] = c.U, cfg[1] = c.nth, cfg[2] = c.rg, cfg[3] = c ? c.gs : 0, cfg[4] = c.variant;
+  return c ? rec6_kernel(fwd, d.mode, d.prec, d.H, c) : nullptr;
+}
 
 // ---- residency gate of the gradient exchange (rnn.h) ----
 namespace {
@@ -4032,8 +1048,8 @@ int rnn_forward_training(const RnnDesc &d, hipStream_t s, int T, int N, const fl
       p.fcopy = p.xpd && chained;
       p.ysc1 = rowchain ? 1 : 0;
       p.allow_local = p.xpd ? 1 : 0;
-      // self-tagged hand-off (the kernel takes it for split-fp16 without IO
-      // waves or a write-through copy): the ring's two images start at tag 1
+      // self-tagged hand-off (the kernel takes it for split-fp16 variants other
+      // than kRec6IoWave, without a write-through copy): the ring starts at tag 1
       p.dtag = d.prec != kPrecBf16 && p.ring == 2 && !p.fcopy && T >= 2;
       if (p.dtag) {  // rnn_fwd_rec6's ring: after T step images of XS = 64 H rg halves (2 dirs, hi / lo, 16 rows)
         const size_t xs = sizeof(_Float16) * 64 * (size_t)d.H * p.rg;
@@ -4053,8 +1069,8 @@ int rnn_forward_training(const RnnDesc &d, hipStream_t s, int T, int N, const fl
     const hipEvent_t fork = (chained || prepack || prepack_w || rowchain) ? fork_event(s) : nullptr;
     {
       ProfSpan ps(s, "rnn_fwd_rec");
-      if (ver == 6) launch6(true, d.mode, d.prec, c6.nth, p, grid, lds, s);
-      else launch_rec(true, d.mode, p, grid, lds, s, ver);
+      if (ver == 6) launch_rec(rec6_kernel(true, d.mode, d.prec, H, c6), p, grid, c6.nth, lds, s);
+      else launch_rec(rec_generic_kernel(true, ver, d.mode, p.Npad / 16), p, grid, NT, lds, s);
     }
     KCTC_HIP_CHECK(hipGetLastError());
     if (ver == 6) rec_scope.enqueued(p);
@@ -4434,8 +1450,8 @@ int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float
     if (ver == 6) p.reg = rw.word;  // registration for the exchange's residency gate
     {
       ProfSpan ps(s, "rnn_bwd_rec");
-      if (ver == 6) launch6(false, d.mode, d.prec, c6.nth, p, grid, lds, s);
-      else launch_rec(false, d.mode, p, grid, lds, s, ver);
+      if (ver == 6) launch_rec(rec6_kernel(false, d.mode, d.prec, H, c6), p, grid, c6.nth, lds, s);
+      else launch_rec(rec_generic_kernel(false, ver, d.mode, p.Npad / 16), p, grid, NT, lds, s);
     }
     KCTC_HIP_CHECK(hipGetLastError());
     if (ver == 6) {
@@ -4660,7 +1676,7 @@ int rnn_backward_weights(const RnnDesc &d, hipStream_t s, int T, int N, const fl
     // overlaps): input^T and output^T are packed and dW runs on s2 while
     // dGates^T is packed and dR runs on s (separate split slabs, tile
     // counters and absmax scratch); s then waits for s2
-    const unsigned *cme0 = pick_bwd_u6(d, N) ? pk<unsigned>(workspace, d, T, N, pl.cme) : nullptr;
+    const unsigned *cme0 = pick6(d, N, false) ? pk<unsigned>(workspace, d, T, N, pl.cme) : nullptr;
     // (LSTM: dR's dGates^T is dW's, E == DX; the GRU's E^T pack stays on one stream)
     const bool two = s2 && x3 && cme0 && d.mode == kLstm && d.layers == 1 && T > 1 && env_int("KCTC_WGRAD_2S", 1);
     hipStream_t sx = two ? s2 : s;  // stream of the input / output packs and of dW

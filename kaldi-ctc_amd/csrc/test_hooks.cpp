@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "gemm.h"
+#include "rnn.h"
 
 extern "C" {
 
@@ -26,6 +27,19 @@ int kcm_test_row_stream(struct ihipStream_t *stream, int M, int N, int K, int fo
     return hipGetLastError() == hipSuccess ? 0 : 3;
   } catch (const std::invalid_argument &) {
     return 1;
+  } catch (...) {
+    return 3;
+  }
+}
+
+int kctc_test_rec6_select(int mode, int prec, int H, int dirs, int N, int fwd, int cfg[6], const void **kernel) {
+  if (!cfg || !kernel) return 1;
+  try {
+    kctc::RnnDesc d;
+    d.mode = mode; d.prec = prec; d.D = d.H = H; d.dirs = dirs;
+    *kernel = kctc::rnn_rec6_select(d, N, fwd != 0, cfg);
+    cfg[5] = kctc::rnn_usable_cus();
+    return 0;
   } catch (...) {
     return 3;
   }

@@ -29,6 +29,12 @@ int kcm_test_row_stream(struct ihipStream_t *stream, int M, int N, int K, int fo
  * streams dx and runs the weight GEMMs on the side stream, as in training. */
 struct kctcComponentImpl;
 int kctc_test_component_side_streams(struct kctcComponentImpl *h, int on);
+/* Which v6 recurrence a layer of (mode, prec, H, dirs) runs at N sequences
+ * (mode: 0 RELU, 1 TANH, 2 LSTM, 3 GRU; fwd: forward or backward-data): cfg =
+ * {U, nth, rg, gs, variant (1 plain, 2 stacked, 3 IO-wave), usable CUs} --
+ * zeros but the last when v6 does not apply -- and *kernel the address of the
+ * kernel the lookup names for it (NULL then).  Nothing is launched. */
+int kctc_test_rec6_select(int mode, int prec, int H, int dirs, int N, int fwd, int cfg[6], const void **kernel);
 #ifdef __cplusplus
 }
 #endif
