@@ -169,12 +169,17 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   // values live and spilled the 512-thread GRU kernel to scratch (before the
   // step loop, but a kernel with scratch must run alone: rec6_scratch_free)
   // ---- per-element state: thread tid <-> (row n0 + en, unit u0 + eu) ----
-  const bool has_e = tid < 16 * U;
+  // STK: a group has at most 8 rows, so the element threads are whole waves
+  // (tid < 8 U) and the others run no coefficients, reduction reads, cell or
+  // bookkeeping; rows 8..15 of the [16][U] reductions behind the loop come
+  // from the has_r threads, as zeros
+  const bool has_r = tid < 16 * U;
+  const bool has_e = tid < (STK ? 8 : 16) * U;
   const int en = tid / U, eu = tid - en * U;
   const int n = n0 + en;
   const bool live = has_e && n < nend;
   float carry = 0.f, bsx[NW], bsh[NW], dxk[NW], eg[NW], cg[NW], ng[NW], cmx[NW], cme[NW];
-  float cdy = 0.f, ca = 0.f, cap = 0.f, ndy = 0.f, na = 0.f, nap = 0.f;
+  float cdy = 0.f, ca = 0.f, cap_ld = 0.f, ndy = 0.f, na = 0.f, nap = 0.f;
   // The cell's coefficients -- everything of the pointwise backward that does
   // not depend on the hand-off -- computed from the step's forward values
   // after the previous step's publish (while the other producers' epochs are
@@ -182,19 +187,32 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   //   LSTM: dc = dh kc[0] + carry, dG_q = dc kc[1+q] (q < 3), dG_3 = dh kc[4], carry = dc kc[5]
   //   GRU : dh += carry, dX_q = dh kc[q], dE_2 = dh kc[3], carry = dh kc[4]
   float kc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  auto coef = [&]() {
+  auto coef = [&](int kk, bool first = false) {  // kk: the forward-order step of c*
+    // (STK: the first frame's previous state is zeroed here, not by the prefetch)
+    const float cap = (!STK || kk > 0) ? cap_ld : 0.f;
+    // (STK: the fused multiply-adds spelled out, as they were contracted
+    // before the two-ahead prefetch -- all of them, but for the LSTM's
+    // 1 - g^2 of the first step (the copy in front of the loop), which had two
+    // roundings and keeps them; left to the compiler, which of them fuse
+    // depends on the code around, and with it the last bit of every result)
+    auto omsq = [](float x) { return STK ? __builtin_fmaf(-x, x, 1.f) : 1.f - x * x; };
+    auto omsq2 = [](float x) {
+      float sq = x * x;
+      asm volatile("" : "+v"(sq));
+      return 1.f - sq;
+    };
     if (MODE == kLstm) {
       const float ig = cg[0], fg = cg[1], gg = cg[2], og = cg[3];
-      const float tc = ftanh(ca);
-      kc[0] = og * (1.f - tc * tc);
+      const float tc = STK ? __builtin_fmaf(2.f, fsigm(2.f * ca), -1.f) : ftanh(ca);
+      kc[0] = og * omsq(tc);
       kc[1] = gg * ig * (1.f - ig);
       kc[2] = cap * fg * (1.f - fg);
-      kc[3] = ig * (1.f - gg * gg);
+      kc[3] = ig * ((STK && first) ? omsq2(gg) : omsq(gg));
       kc[4] = tc * og * (1.f - og);
       kc[5] = fg;
     } else {
       const float r = cg[0], z = cg[1], nn = cg[2];
-      const float kn = (1.f - z) * (1.f - nn * nn);
+      const float kn = (1.f - z) * omsq(nn);
       kc[0] = kn * ca * r * (1.f - r);
       kc[1] = (cap - nn) * z * (1.f - z);
       kc[2] = kn;
@@ -254,14 +272,37 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
 #pragma unroll
       for (int q = 0; q < NW; q++) ng[q] = g_p[q * H];
       na = *aux_p;
-      nap = k > 0 ? *prv_p : 0.f;
+      if constexpr (STK) {
+        // always loaded (first frame: a valid address, the value dropped by
+        // coef()): a conditional load here tied nap to a zero in a register
+        // pair and put a vmcnt(0) behind the loads
+        const gcfp pp = k > 0 ? prv_p : aux_p;
+        nap = *pp;
+      } else {
+        nap = k > 0 ? *prv_p : 0.f;
+      }
     }
     dy_p += ystep; g_p += gstep; aux_p += ystep; prv_p += ystep;
   };
+  // STK: the operands run two steps ahead.  Step ks loads those of step
+  // ks + 2 into n* behind its hand-off wait; directly before, behind that same
+  // wait (in-order vmcnt: it retired the loads of step ks - 1 too), n* -- the
+  // operands of step ks + 1 -- rotate into c*, where coef() of step ks + 1
+  // finds them a whole step old.  The cell of step ks runs after that rotate:
+  // its dy waits one stage longer, in xdy.
+  float xdy = 0.f;
   auto rotate = [&]() {
-    cdy = ndy; ca = na; cap = nap;
+    xdy = cdy;
+    cdy = ndy; ca = na; cap_ld = nap;
 #pragma unroll
     for (int q = 0; q < NW; q++) cg[q] = ng[q];
+    if constexpr (STK) {
+      // one register each (as pairs, a half copied behind the prefetch's
+      // loads put a vmcnt(0) there)
+      asm volatile("" : "+v"(cdy), "+v"(ca), "+v"(cap_ld));
+#pragma unroll
+      for (int q = 0; q < NW; q++) asm volatile("" : "+v"(cg[q]));
+    }
   };
   // bf16 packed operands (p.dxt): the step's DX tile is staged in estg and the
   // GRU's E tile in estg2 during the cell phase; the next step writes them as
@@ -349,7 +390,16 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   const int ereg = STK ? (eu & 3) : (en & 3);
   prefetch(T - 1);
   rotate();
-  if constexpr (PRE) coef();
+  if constexpr (STK) {
+    if (T > 1) prefetch(T - 2);
+    // landed before the loop: step 0 has no hand-off wait to rotate behind
+    asm volatile("" : "+v"(ndy), "+v"(na), "+v"(nap));
+#pragma unroll
+    for (int q = 0; q < NW; q++) asm volatile("" : "+v"(ng[q]));
+  }
+  if constexpr (PRE) {
+    if (!STK || has_e) coef(T - 1, true);
+  }
   int bad = 0;
   unsigned *myflag = flag6(p, grp, d, g, NWG);
   // XCD-slot launches keep the hand-off in the XCD's L2 (plain flag stores
@@ -385,7 +435,11 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   // flag store or flag poll -- the poll IS the payload load.  Ring safety as
   // before: a producer writes slot ks % 2 only after it has read every
   // consumer's step ks - 1 words, stored after that consumer's loads of step
-  // ks - 2 had returned.
+  // ks - 2 had returned.  Nothing here rests on a wait at the end of a step
+  // (STK has none): a consumer's loads of step ks - 2 are retired by its own
+  // poll's vmcnt(0), every wave's, before the step's first barrier, and its
+  // step ks - 1 words follow its second; a wave's stores to one slot, two
+  // steps apart, have the poll between them retiring the older.
   const bool dtag = !BF && p.dtag && local && p.ring == 2;
   // step t's DX rows for a streaming consumer on other XCDs, from the LDS
   // stage: written through (sc1) as whole 16-B chunks, 4 lanes per
@@ -431,7 +485,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
                      rs, crow_live ? (int)((coff + (long)i * NGRP * PSTR) * 4) : 0x7fff0000, 0, 16 /* sc1 */));
         if constexpr (PRE) {
           __builtin_amdgcn_sched_barrier(0);
-          coef();  // while the hand-off loads are in flight
+          coef(k);  // while the hand-off loads are in flight
           __builtin_amdgcn_sched_barrier(0);
         } else if (kEarlyE) {
           // bf16: the previous step's dGates rows / packed operands (its
@@ -457,7 +511,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
         for (int i = 0; i < PER; i++) v[i] = ld_sc1(rs, hoff(i));
         if constexpr (PRE) {
           __builtin_amdgcn_sched_barrier(0);
-          coef();  // while the hand-off loads are in flight
+          if (!STK || has_e) coef(k);  // while the hand-off loads are in flight
           // (pinned here: IR passes had sunk the coefficients past the loads' wait)
 #pragma unroll
           for (int q = 0; q < 6; q++) asm volatile("" : "+v"(kc[q]));
@@ -497,6 +551,10 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
       st4(red + (long)(pg * POS + pos) * 4, sm);
       REC_TRACE(ks, 2);
       REC_TRACE_W(ks, 24);
+      // behind the hand-off wait, which retired the last step's prefetch too
+      // (on this path: a rotate behind the branches' join waits again, for
+      // the loads the compiler must assume on the path without a hand-off)
+      if constexpr (STK) rotate();
       // behind this step's hand-off loads: the write-through copies for the
       // streamed dx GEMM -- the previous step's dGates rows (staged in LDS)
       // and the epoch the last signal drained (step ks - 2's rows).  Issued
@@ -505,17 +563,31 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
       // (self-tagged: after the barrier below, which orders it behind the
       // previous step's book() writes of estg -- no signal barrier in between)
       if (p.e_sc1 && !dtag) e_sc1_store(t_prev);
+    } else {
+      if constexpr (STK) rotate();  // step 0: nothing outstanding (see the prologue)
     }
     asm volatile("" ::: "memory");
     // behind the hand-off loads: next step's operands, last step's row-major dGates
     if (t_prev >= 0 && !(kEarlyE && !PRE && bfp && ks > 0)) e_store(t_prev);
-    if (k > 0) prefetch(k - 1);
+    if constexpr (STK) {
+      if (k > 1) prefetch(k - 2);
+    } else {
+      if (k > 0) prefetch(k - 1);
+    }
     __syncthreads();
     REC_TRACE(ks, 8);
-    if (bad_lds) bad = 1;
-    // self-tagged: every producer's words of step ks - 1 were stored after its
-    // poll of step ks - 2 had retired (in-order vmcnt) its write-through rows
-    // of step ks - 3 -> epoch ks (rows of step k out at epoch k + 3);
+    // (STK: read here, looked at behind the cell -- the loop condition is its
+    // only reader, and the LDS returns in order, so the element waves' red
+    // reads do not wait for it)
+    int bl = 0;
+    if constexpr (STK) bl = bad_lds;
+    else if (bad_lds) bad = 1;
+    // self-tagged: every producer's words of step ks - 1 were stored behind
+    // its second barrier of that step, which every wave reached after its
+    // poll -- the hand-off loads' vmcnt(0), in order -- had retired the
+    // write-through rows it issued in step ks - 2, those of step ks - 3
+    // -> epoch ks (rows of step k out at epoch k + 3; no wait at the end of
+    // a step is part of this);
     // flagged: its signal of step ks - 1 drained the rows of step ks - 2
     if (gflag && ks > 0 && tid == 0)
       __hip_atomic_store(gflag, (unsigned)(dtag ? ks : ks + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -532,7 +604,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
 #pragma unroll
         for (int gg = 0; gg < NGRP; gg++) dhr += rr[gg];
       }
-      float dh = cdy + dhr;
+      float dh = (STK ? xdy : cdy) + dhr;
       if constexpr (PRE) {
         if (MODE == kLstm) {
           const float dc = dh * kc[0] + carry;
@@ -541,6 +613,13 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
           eg[2] = dc * kc[3];
           eg[3] = dh * kc[4];
           carry = dc * kc[5];
+          if constexpr (STK) {
+            // scalar products: packed with a broadcast dc, the unused half of
+            // the pair fell on a register the prefetch is loading, and the
+            // cell waited for the loads (vmcnt(0))
+#pragma unroll
+            for (int q = 0; q < NW; q++) asm volatile("" : "+v"(eg[q]));
+          }
         } else {
           dh += carry;
           dxk[0] = dh * kc[0]; dxk[1] = dh * kc[1]; dxk[2] = dh * kc[2];
@@ -553,14 +632,14 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
         const float dO = dh * tc;
         const float dc = dh * og * (1.f - tc * tc) + carry;
         eg[0] = dc * gg * ig * (1.f - ig);
-        eg[1] = dc * cap * fg * (1.f - fg);
+        eg[1] = dc * cap_ld * fg * (1.f - fg);
         eg[2] = dc * ig * (1.f - gg * gg);
         eg[3] = dO * og * (1.f - og);
         carry = dc * fg;
       } else {
         dh += carry;
         const float r = cg[0], z = cg[1], nn = cg[2];
-        const float dn = dh * (1.f - z), dz = dh * (cap - nn);
+        const float dn = dh * (1.f - z), dz = dh * (cap_ld - nn);
         const float dpn = dn * (1.f - nn * nn);
         const float dpr = dpn * ca * r * (1.f - r);
         const float dpz = dz * z * (1.f - z);
@@ -586,7 +665,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
         for (int q = 0; q < NW; q++) split16(ldexpf(eg[q], se), hh[q], hl[q]);
         _Float16 *dhi = Ahi + en * AP + eu * NW;
         _Float16 *dlo = STK ? Ahi + (en + 8) * AP + eu * NW : Alo + en * AP + eu * NW;
-        if (!STK || en < 8) {
+        {
           if constexpr (NW == 4) {
             typedef _Float16 half4 __attribute__((ext_vector_type(4)));
             *reinterpret_cast<half4 *>(dhi) = half4{hh[0], hh[1], hh[2], hh[3]};
@@ -601,6 +680,9 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
         }
         if (eu == 0) rowexp[en] = se + sB;
       }
+    }
+    if constexpr (STK) {
+      if (bl) bad = 1;
     }
     REC_TRACE(ks, 12);
     __syncthreads();
@@ -785,7 +867,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
     REC_TRACE(ks, 7);
     if (!dtag) signal_epoch(myflag, (unsigned)(ks + 2), local);
     REC_TRACE(ks, 4);
-    rotate();
+    if constexpr (!STK) rotate();
     t_prev = t;
     REC_TRACE(ks, 5);
   }
@@ -803,7 +885,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   // order through LDS; the host adds the groups in order
   float *bs = red;  // [2][16][U][NW] floats
   __syncthreads();
-  if (has_e) {
+  if (has_r) {
 #pragma unroll
     for (int q = 0; q < NW; q++) {
       const long b0 = ((long)en * U + eu) * NW + q;
@@ -821,7 +903,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   if (p.cmax) {  // column maxima over all frames (this group's rows, through LDS; max over groups)
     constexpr int NP = MODE == kGru ? 2 : 1;
     __syncthreads();
-    if (has_e) {
+    if (has_r) {
 #pragma unroll
       for (int q = 0; q < NW; q++) {
         bs[((long)en * U + eu) * NW + q] = cmx[q];
