@@ -287,6 +287,52 @@ def find_row_max_id(m, stream=None):
     return ids
 
 
+def _f32_dev(*tensors):
+    import torch
+    for t in tensors:
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+
+
+def clip_gradient_rows(deriv, threshold, num_clipped, stream=None):
+    """kcm_clip_gradient_rows in place on a 2-D torch CUDA float32 tensor: rows
+    with |row| >= threshold are rescaled to norm threshold, and num_clipped (a
+    CUDA int32 tensor of one element) rises by their number."""
+    import torch
+    _f32_dev(deriv)
+    assert deriv.dim() == 2 and num_clipped.is_cuda and num_clipped.dtype == torch.int32 and num_clipped.numel() == 1
+    st = lib().kcm_clip_gradient_rows(_stream_handle(stream), _ptr(deriv), deriv.shape[0], deriv.shape[1],
+                                      float(threshold), _ptr(num_clipped))
+    if st != 0:
+        raise KctcError(f"kcm_clip_gradient_rows failed ({st})")
+
+
+def add_vec_clipped(w, dw, lr, clip, stream=None):
+    """w += lr * clamp(dw, -clip, clip) on 1-D torch CUDA float32 tensors of one
+    length (clip <= 0: no clamp) (kcm_add_vec_clipped)."""
+    _f32_dev(w, dw)
+    assert w.dim() == 1 and w.shape == dw.shape
+    st = lib().kcm_add_vec_clipped(_stream_handle(stream), _ptr(w), _ptr(dw), w.numel(), float(lr), float(clip))
+    if st != 0:
+        raise KctcError(f"kcm_add_vec_clipped failed ({st})")
+
+
+def add_row_sum_mat(out, X, alpha=1.0, beta=0.0, ws=None, stream=None):
+    """CuVector::AddRowSumMat: out [cols] = alpha * (sum of the rows of X
+    [rows, cols]) + beta * out; ws: >= 64 * cols floats of device scratch
+    (allocated when None) (kcm_add_row_sum_mat)."""
+    import torch
+    _f32_dev(out, X)
+    assert X.dim() == 2 and out.dim() == 1 and out.numel() == X.shape[1]
+    if ws is None:
+        ws = torch.empty(64 * X.shape[1], dtype=torch.float32, device=X.device)
+    _f32_dev(ws)
+    assert ws.numel() >= 64 * X.shape[1]
+    st = lib().kcm_add_row_sum_mat(_stream_handle(stream), _ptr(X), X.shape[0], X.shape[1], float(alpha),
+                                   float(beta), _ptr(out), _ptr(ws))
+    if st != 0:
+        raise KctcError(f"kcm_add_row_sum_mat failed ({st})")
+
+
 # ---------------------------------------------------------------------------
 # nnet2 trainer (include/kaldi_ctc_train.h)
 # ---------------------------------------------------------------------------

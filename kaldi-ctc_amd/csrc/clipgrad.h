@@ -23,7 +23,8 @@ void clipgrad_backprop(hipStream_t s, float *d, const float *in_value, long rows
                        float threshold, bool norm_based, bool try_repair, float repair_threshold,
                        float repair_target, float repair_scale, ClipState *st, void *scratch,
                        const ClipState *decide = nullptr);
-// st accumulates the counters; decide (default st) supplies the clipped
+// st accumulates the counters (null: Backprop without a to_update -- clip only,
+// no state is written); decide (default st) supplies the clipped
 // proportion of the repair decision: the backpropped component's own stats,
 // which differ from to_update's under momentum (ctc-nnet-train.cc:194-202).
 

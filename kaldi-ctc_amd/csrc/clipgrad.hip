@@ -83,7 +83,9 @@ __global__ __launch_bounds__(256) void k_decide(State *st, const State *dec, con
   b = block_sum(b);
   if (threadIdx.x == 0) {
     const double prop = dec->count > 0 ? dec->num_clipped / dec->count : 0.0;
-    st->active = prop > (double)threshold;
+    // the decision in BaseFloat, as the reference takes it (:995-1000):
+    // 1 / 100 against 0.01f is a tie there, and a tie does not repair
+    st->active = dec->count > 0 && (float)dec->num_clipped / (float)dec->count > threshold;
     st->dn = a;
     st->rn = b;
     st->scale = 0.0;
@@ -141,7 +143,11 @@ void clipgrad_backprop(hipStream_t s, float *d, const float *in_value, long rows
                        const ClipState *decide) {
   if (!decide) decide = st;
   if (rows <= 0 || !(threshold > 0.f)) return;
-  if (norm_based) {
+  if (norm_based && !st) {
+    // to_update == NULL (:953-957): clip, count nowhere -- the row kernel's
+    // count lands in the scratch, which nothing reads without a repair
+    rownorm_clip(s, d, rows, dim, threshold, static_cast<int *>(scratch));
+  } else if (norm_based) {
     rownorm_clip(s, d, rows, dim, threshold, &st->step_clipped);
     hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, s, st, rows);
   } else {
@@ -149,7 +155,7 @@ void clipgrad_backprop(hipStream_t s, float *d, const float *in_value, long rows
     hipLaunchKernelGGL(k_clamp, dim3((int)std::min<long>(4096, (n + 255) / 256)), dim3(256), 0, s, d,
                        n, threshold);
   }
-  if (!try_repair) return;
+  if (!try_repair || !st) return;  // RepairGradients runs only with a to_update (:965-968)
   double *part = static_cast<double *>(scratch);
   const int nb = ceil_div(rows, 4);
   hipLaunchKernelGGL(k_norms, dim3(nb), dim3(256), 0, s, d, in_value, rows, dim, repair_target, 1,

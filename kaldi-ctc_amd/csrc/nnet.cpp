@@ -906,7 +906,7 @@ void ClipGradientComponent::Backprop(const ChunkInfo &, const ChunkInfo &, const
   scratch_.ensure(clipgrad_scratch_bytes(rows));
   clipgrad_backprop(S(), in_deriv->Data(), in_value.Data(), rows, dim_, clipping_threshold_,
                     norm_based_clipping_, try_repair, self_repair_clipped_proportion_threshold_,
-                    self_repair_target_, self_repair_scale_, (to_update ? to_update : this)->dev_,
+                    self_repair_target_, self_repair_scale_, to_update ? to_update->dev_ : nullptr,
                     scratch_.p, dev_);
 }
 
