@@ -78,7 +78,7 @@ struct X3PArgs {
   float *stream_part = nullptr;         // [row tiles][batch][col tiles][128 x 128] half-K partials
   long stream_group_step = 0;         // halves per row group's part of a step image
   unsigned *stream_err = nullptr;    // set (bit 2) if the producer stops publishing
-  // XCD-pinned producer (rnn.hip xcd_mask): blocks on its XCDs exit before
+  // XCD-pinned producer (rnn_plan.hip xcd_mask): blocks on its XCDs exit before
   // taking work, as in X3PBwdStream
   const unsigned *stream_xcd_word = nullptr;
   int stream_xcd_count = 0;
@@ -88,7 +88,7 @@ struct X3PArgs {
   bool bf16 = false;
   // Beside an XCD-pinned recurrence (non-gated, non-streaming 256-tile GEMMs
   // with a tile counter): blocks whose XCD has its bit set in *avoid_word
-  // (rnn.hip rnn_pinned_xcds: the XCDs pinned backward recurrences ran on)
+  // (rec_gate.hip rnn_pinned_xcds: the XCDs pinned backward recurrences ran on)
   // exit before taking work, so no block ever holds a CU the recurrence
   // needs and the launch ends when the other XCDs' blocks run out of tiles
   // (no block exits while the word names all avoid_xcds XCDs of the device:
@@ -97,7 +97,7 @@ struct X3PArgs {
   int avoid_xcds = 8;
 };
 void gemm_x3p(hipStream_t s, const X3PArgs &g);
-// rnn.hip: s passed the residency gate of the recurrence in flight (or none is)
+// rec_gate.hip: s passed the residency gate of the recurrence in flight (or none is)
 bool rnn_side_gated(hipStream_t s);
 // two independent 256-tile problems (e.g. a layer's dW and dR) as ONE launch
 // sharing g1's tile counter, then each one's split-K reduction: beside a
@@ -145,7 +145,7 @@ struct X3PBwdStream {
   unsigned *err = nullptr;
   int blocks = 0;                      // persistent blocks (each takes a CU: 96 KB LDS)
   bool bf16 = false;                   // rows packed as bf16 ([M][KB][64], KB 64-k blocks), B bf16, no exponents
-  // XCD-pinned producer (rnn.hip xcd_mask): its workgroups OR
+  // XCD-pinned producer (rnn_plan.hip xcd_mask): its workgroups OR
   // 1 << XCC_ID into *xcd_word as they start; a block waits until
   // xcd_count XCDs are registered and exits if it is on one of them
   const unsigned *xcd_word = nullptr;

@@ -1,5 +1,6 @@
 // rec_common.h -- what the recurrence kernels (rec_generic.hip: v3 / v4,
-// rec6_fwd.hip, rec6_bwd.hip: v6) and their host (rnn.hip) share: RecParams,
+// rec6_fwd.hip, rec6_bwd.hip: v6) and their host (rnn.hip, rnn_plan.hip,
+// rec_gate.hip) share: RecParams,
 // the hand-off helpers, trace stamps, the named flag words; V6Cfg and the
 // kernel lookups.  The unnamed namespace's contents are per translation unit.
 #pragma once
@@ -14,7 +15,7 @@ namespace kctc {
 // (kPrecX3 / kPrecBf16), stacked (kPrecX3S: hi / lo of a <= 8-row group in one
 // MFMA operand) or IO-wave (P | 4, forward only: the upper waves fetch G)
 enum Rec6Variant { kRec6None = 0, kRec6Plain = 1, kRec6Stacked = 2, kRec6IoWave = 3 };
-// One v6 configuration of a (descriptor, N, direction of time): pick6 (rnn.hip)
+// One v6 configuration of a (descriptor, N, direction of time): pick6 (rnn_plan.hip)
 struct V6Cfg {
   int U = 0, nth = 0, rg = 0, gs = 16, variant = kRec6None;
   explicit operator bool() const { return U > 0; }
@@ -342,22 +343,29 @@ __device__ __forceinline__ float group_maxU(float v, int U) {
 // producers' flag stores and the consumers' polls spread over L2 / memory
 // channels instead of hammering one line.
 constexpr int kFlagStride = 32;  // words
-// word of the flag area where an XCD-pinned backward recurrence's workgroups
-// OR in 1 << XCC_ID (words 1008 / 1009: weight-gradient tile counters)
+// Words of the flag area (zeroed before every recurrence launch) with a name.
+// Host side, after the component's recurrences are done: the dynamic tile
+// counters of the dW / dR weight GEMMs and the item counters of their packs
+constexpr int kTileWordW = 1008, kTileWordR = 1009;
+constexpr int kPackWord = 1010, kPackWords = 5;  // 1010..1014
+// where an XCD-pinned backward recurrence's workgroups OR in 1 << XCC_ID
 constexpr int kXcdWord = 1016;
 constexpr int kResWord = 1017;  // v6 recurrence: workgroups resident so far (beside_recurrence)
 constexpr int kGateWord = 1018;  // blocks of its residency gate that left (rnn_resident_gate)
-// the named words: apart, clear of the tile and item counters (1008..1014)
-// and inside the words zeroed before every launch (v6 flag lines start at 1024)
-static_assert(kXcdWord > 1014 && kXcdWord < kResWord && kResWord < kGateWord && kGateWord < 1024,
-              "named flag words: distinct, above the counters, below 1024");
+constexpr int kFlag6Word = 1024;  // the first v6 flag line
+constexpr int kAggLine = 256;     // the first aggregated line, counted from kFlag6Word (agg_flag6)
+// the named words: apart, the host's counters below the recurrence's words,
+// all inside the words below the v6 flag lines
+static_assert(kTileWordW < kTileWordR && kTileWordR < kPackWord && kPackWord + kPackWords <= kXcdWord &&
+                  kXcdWord < kResWord && kResWord < kGateWord && kGateWord < kFlag6Word,
+              "named flag words: distinct, the counters below the recurrence's words, all below the v6 flag lines");
 __device__ __forceinline__ unsigned *flag6(const RecParams &p, int grp, int d, int g, int nwg) {
-  return p.flags + 1024 + (((long)grp * p.dirs + d) * nwg + g) * kFlagStride;
+  return p.flags + kFlag6Word + (((long)grp * p.dirs + d) * nwg + g) * kFlagStride;
 }
 // aggregated epoch of (row group, direction) for the streamed GEMMs of an
 // XCD-pinned recurrence: one line each, 256 lines past the flag lines
 __device__ __forceinline__ unsigned *agg_flag6(const RecParams &p, int grp, int d) {
-  return p.flags + 1024 + (256 + (long)grp * p.dirs + d) * kFlagStride;
+  return p.flags + kFlag6Word + (kAggLine + (long)grp * p.dirs + d) * kFlagStride;
 }
 __device__ __forceinline__ void wait_flags6(const unsigned *f0, int nwg, unsigned epoch, unsigned *err, int &bad,
                                             int *bad_lds, int sleep = 1) {

@@ -68,6 +68,12 @@ int rnn_comm_cus();
 // variant} of the v6 recurrence that (d, N, fwd) runs (zeros: not a v6 shape)
 // and its kernel (nullptr then); nothing is launched
 const void *rnn_rec6_select(const RnnDesc &d, int N, bool fwd, int cfg[5]);
+// test hook (test_hooks.h kctc_test_rec_plan): the whole plan of the
+// recurrence that (d, N, fwd) runs, any version: plan = {version (6 / 4 / 3;
+// 0: not supported, the rest zeros), U, grid (workgroups), threads per
+// workgroup, dynamic LDS bytes, XCDs a pinned v6 launch occupies (bit mask),
+// workgroups per (row group, direction), RecParams::xpd}; nothing is launched
+void rnn_rec_plan(const RnnDesc &d, int N, bool fwd, long plan[8]);
 
 // Residency gate of the gradient exchange.  Every workgroup
 // of a v6 backward recurrence adds 1 to a per-device 64-bit registration
@@ -79,14 +85,14 @@ const void *rnn_rec6_select(const RnnDesc &d, int N, bool fwd, int cfg[5]);
 // a block on an XCD a recurrence is pinned to leaves (unless it is the last
 // one waiting), so that no gate wave holds a CU a workgroup of that
 // recurrence needs -- a workgroup that takes a CU's whole register file
-// cannot be placed beside one (rnn.hip gate_kernel).  An exchange
+// cannot be placed beside one (rec_gate.hip gate_kernel).  An exchange
 // that runs its kernels only behind such a gate -- i.e. only while the
 // backward recurrence launched last is fully resident -- and makes the next
 // recurrence launch wait for them declares rnn_set_comm_gated(true): the
 // backward recurrences then stay XCD-pinned with an exchange configured.
 unsigned long long rnn_bwd_registrations();
 // false when the backward recurrence this thread enqueued last uses scratch:
-// nothing may then be queued beside it (rnn.hip rec6_scratch_free), so the
+// nothing may then be queued beside it (rnn_plan.hip rec6_scratch_free), so the
 // exchange waits for its end instead of its residency
 bool rnn_last_bwd_scratch_free();
 void rnn_comm_gate(hipStream_t s, unsigned long long target);
@@ -99,7 +105,7 @@ void rnn_resident_gate(hipStream_t s, const unsigned *flags, unsigned target);
 // before the launch).  Each kernel that rnn.hip puts on another stream while
 // that recurrence runs -- the streamed GEMMs, the wgrad chunk gates, the
 // forward-time packs -- is enqueued behind a gate kernel waiting for that count
-// (rnn.hip beside_recurrence): nothing there can take a CU before every
+// (rec_gate.hip beside_recurrence): nothing there can take a CU before every
 // workgroup of the recurrence holds its own, so a consumer spinning on the
 // recurrence's progress cannot keep a producer workgroup out.  The host
 // refuses a streaming launch (gemm_x3p with stream_flags,

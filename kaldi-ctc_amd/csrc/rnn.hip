@@ -8,7 +8,7 @@
 //   1. G = x W^T + bW (+ bR): the input projection of all T*N frames of both
 //      directions as one packed split-fp16 GEMM (gemm_x3p.hip) -- or, for the
 //      layers above the first, streamed off the previous component's running
-//      recurrence (launch_chain_proj).
+//      recurrence (launch_chain_proj / launch_chain_rows).
 //   2. rnn_fwd_rec6: ONE persistent launch runs the whole time recurrence of
 //      both directions (and of every row group of 8 or 16 sequences).  Work-
 //      group (group, dir, g) owns hidden units [g*U, g*U+U); its slice of R
@@ -31,15 +31,26 @@
 //   dW += dGx^T x, dR += dGh^T h_prev (time-shifted views), packed split-fp16
 //   GEMMs on a side stream beside the next component's backward recurrence;
 //   bias sums accumulated by the recurrence.
-// Hand-off protocol (both recurrences): payload sc1 stores -> every storing
-// wave's s_waitcnt vmcnt(0) -> workgroup barrier -> lane 0 stores the step
-// epoch into the workgroup's own 128-B flag line; consumers poll the flag
-// lines of their producers, then sc1 loads (MI355X_MICROARCH.md "Valid forms",
-// row 1).  Every spin is bounded (3 s); a timeout sets the device error word,
-// every workgroup drains out and the train step fails loudly.
+// Hand-off protocols of the v6 recurrences (the kernel files have the detail):
+//   flagged: payload sc1 stores -> every storing wave's s_waitcnt vmcnt(0) ->
+//     workgroup barrier -> lane 0 stores the step epoch into the workgroup's
+//     own 128-B flag line; consumers poll the flag lines of their producers,
+//     then sc1 loads (MI355X_MICROARCH.md "Valid forms", row 1).  The bf16
+//     recurrences, the unpinned ones, the IO-wave forward and a pinned forward
+//     that copies its images for a streamed projection hand off this way.
+//   self-tagged (RecParams::dtag): the XCD-pinned split-fp16 recurrences hand
+//     off through a ring of two step images in their XCD's L2 whose words
+//     carry the step's tag themselves; the consumers poll the payload, no
+//     flag store and no drain before it.  The epoch lines are still written
+//     for the streamed GEMMs outside the XCD (epoch_lines).
+// Every spin is bounded (3 s); a timeout sets the device error word, every
+// workgroup drains out and the train step fails loudly.
 // v4 (fp32 MFMA, XCD-slot all-gather) and v3 remain for the shapes v6 does
-// not compile (RELU / TANH, other H, N > 64).  This file is the host side; the
-// kernels: rec6_fwd.hip, rec6_bwd.hip, rec_generic.hip (v3 / v4), rec_common.h.
+// not compile (RELU / TANH, other H, N > 64).  This file is the host side of
+// the three entry points; which recurrence runs and where the workspace's
+// parts lie: rnn_plan.hip (plan_rec, RnnWs); what may run beside a
+// recurrence: rec_gate.hip; the kernels: rec6_fwd.hip, rec6_bwd.hip,
+// rec_generic.hip (v3 / v4), rec_common.h.
 //
 // Semantics follow cuDNN v5 as used by CuDNNRecurrentComponent: hx = cx = 0,
 // dhy = dcy = 0 (SetBufferZero, nnet-cudnn-component.cc:494-506), all N
@@ -49,10 +60,8 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
-#include <map>
 #include <mutex>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -60,7 +69,9 @@
 #include "gemm.h"
 #include "prof.h"
 #include "rec_common.h"
+#include "rec_gate.h"
 #include "rnn.h"
+#include "rnn_plan.h"
 
 namespace kctc {
 
@@ -82,7 +93,6 @@ long RnnDesc::lin_offset(int p, int lin, bool bias) const {
   return off + n * H * (long)di + n * H * (long)H + (long)lin * H;
 }
 
-static long al64(long x) { return (x + 63) / 64 * 64; }
 void rnn_set_precision(RnnDesc &d, int prec) {
   d.prec = prec;
   const char *e = getenv("KCTC_BF16_DIRECT");
@@ -91,158 +101,26 @@ void rnn_set_precision(RnnDesc &d, int prec) {
   d.pkio = !e || atoi(e) != 0;
 }
 
-RnnReserveLayout rnn_reserve_layout(const RnnDesc &d, int T, int N) {
-  RnnReserveLayout r;
-  const long TN = (long)T * N, nw = d.nw(), H = d.H, dirs = d.dirs;
-  long p = 0;
-  r.G = p;    p += al64(TN * dirs * nw * H);
-  r.aux = p;  p += al64(TN * dirs * H);
-  r.E = p;    p += al64(TN * dirs * nw * H);
-  r.DX = p;   p += (d.mode == kGru) ? al64(TN * dirs * nw * H) : 0;
-  r.bias = p; p += al64(dirs * 2 * nw * H * (long)((N + 7) / 8));  // v6: per row group (>= 8 rows each)
-  r.out = p;  p += (d.layers > 1) ? al64(TN * dirs * H) : 0;
-  r.dout = p; p += (d.layers > 1) ? al64(TN * dirs * H) : 0;
-  r.kbt64 = (TN + 63) / 64 * 64;
-  const bool pkd = d.prec == kPrecBf16 && d.layers == 1 && d.pk;  // bf16 halves: 2 per float
-  const long G4 = nw * H, kbg64 = (G4 + 63) / 64 * 64;
-  r.pkxr = p; p += pkd ? al64((dirs * TN * kbg64 + 1) / 2) : 0;
-  r.pkxt = p; p += pkd ? al64((dirs * G4 * r.kbt64 + 1) / 2) : 0;
-  const bool io = pkd && d.layers == 1 && dirs == 2;  // bf16_io: E^T shifted, apart from DX^T
-  r.pket = p; p += (pkd && (d.mode == kGru || io)) ? al64((dirs * G4 * r.kbt64 + 1) / 2) : 0;
-  r.pkyr = p; p += io ? al64((TN * dirs * H + 1) / 2) : 0;
-  r.pkyc = p; p += io ? al64((dirs * H * r.kbt64 + 1) / 2) : 0;
-  r.per_layer = p;
-  r.total = p * d.layers;
-  return r;
-}
-
-static long drec_split_floats(const RnnDesc &d, int T, int N) {
-  // the dR and dW split slabs of a layer side by side: with a second stream
-  // (rnn_backward_weights' s2) the two GEMMs run concurrently
-  long need = 0, needR = 0, needW = 0;
-  const int G4 = d.nw() * d.H;
-  const int KB = (int)(((long)T * N + 31) / 32);  // packed k blocks over the frames (x3; bf16 needs fewer)
-  for (int l = 0; l < d.layers; l++) {
-    const long K = (long)(T > 1 ? T - 1 : 1) * N;
-    int s = std::max(gemm_pick_split(G4, d.H, (int)K, d.dirs), x3p_pick_split(G4, d.H, KB, d.dirs));
-    if (s > 1) needR = std::max(needR, (long)s * d.dirs * G4 * d.H);
-    s = std::max(gemm_pick_split(G4, d.din(l), (int)((long)T * N), d.dirs), x3p_pick_split(G4, d.din(l), KB, d.dirs));
-    if (s > 1) needW = std::max(needW, (long)s * d.dirs * G4 * d.din(l));
-  }
-  need = al64(needR) + needW;
-  return need;
-}
-
-// split-K slabs of the weight-gradient GEMMs, then the recurrence flag words
-static size_t flags_offset(const RnnDesc &d, int T, int N) {
-  return sizeof(float) * (size_t)al64(drec_split_floats(d, T, N));
-}
-// then the v4 exchange images (one layer at a time; forward and backward of a
-// layer never overlap): T * dirs * max(H, nW*H) * Npad floats
-// flag region: words 0..1023 (v3/v4 flags, placement ids, GEMM tile counters
-// at 1008/1009), then one 128-B line per (direction, workgroup) for v6
-constexpr size_t kFlagBytes = 4096 + 512 * 128;  // v6: up to 4 row groups x 2 dirs x 64 workgroups
-static size_t xch_offset(const RnnDesc &d, int T, int N) { return flags_offset(d, T, N) + kFlagBytes; }
-static size_t xch_bytes(const RnnDesc &d, int T, int N) {
-  const long Npad = (N + 15) / 16 * 16;
-  // v4 images: 4 B x dirs x nW x H x Npad per step; the v6 forward's
-  // [2 dirs][H/32][hi, lo][16][32] halves per row group of <= 16 rows (at most
-  // 2 Npad / 16 groups): 16 B x H x Npad.  + 2 steps: the v6 forward's ring of
-  // hand-off images after its T step images
-  const size_t per = std::max<size_t>(sizeof(float) * d.dirs * d.nw(), 16);
-  return per * (size_t)(T + 2) * d.H * Npad;
-}
-// then the packed split-fp16 GEMM operands of one layer at a time (forward,
-// backward-data and the weight GEMMs of a component never overlap):
-//   forward   : input rows [TN][Din], W rows [dirs*G][Din]
-//   bwd data  : dGates rows [dirs*TN][G], W^T rows [dirs*Din][G]
-//   bwd weight: dGates^T [dirs*G][TN] (+ GRU: E^T), input^T [Din][TN],
-//               shifted output^T [dirs*H][TN]
-// plus int exponents and float-bit column maxima (G = nW*H).
-struct PackLay {
-  size_t a, b, c, d, ea, eb, ec, ed, cm, part, cnt, part2, cme, fcnt, fpart, wt, ewt, cmw, xt, yt, ext, eyt, pcnt, total;
-};
-static PackLay pack_layout(const RnnDesc &d, int T, int N) {
-  const long TN = (long)T * N, G = (long)d.nw() * d.H, Dm = std::max(d.D, d.dirs * d.H), dirs = d.dirs;
-  const size_t fw_a = x3p_bytes(TN, Dm), fw_b = x3p_bytes(dirs * G, Dm);
-  const size_t bd_a = x3p_bytes(dirs * TN, G), bd_b = x3p_bytes(dirs * Dm, G);
-  const size_t bw_a = x3p_bytes(dirs * G, TN) * (d.mode == kGru ? 2 : 1), bw_b = x3p_bytes(Dm, TN),
-               bw_c = x3p_bytes(dirs * d.H, TN);
-  PackLay p;
-  size_t o = 0;
-  p.a = o; o = align_up(o + std::max({fw_a, bd_a, bw_a}), 256);
-  p.b = o; o = align_up(o + std::max({fw_b, bd_b, bw_b}), 256);
-  p.c = o; o = align_up(o + bw_c, 256);
-  p.d = o;  // unused slot kept for symmetry (0 bytes)
-  const long ne = std::max({TN * dirs, dirs * G * 2, dirs * Dm}) + 64;
-  p.ea = o; o = align_up(o + sizeof(int) * ne, 256);
-  p.eb = o; o = align_up(o + sizeof(int) * ne, 256);
-  p.ec = o; o = align_up(o + sizeof(int) * ne, 256);
-  p.ed = o; o = align_up(o + sizeof(int) * ne, 256);
-  p.cm = o; o = align_up(o + sizeof(unsigned) * ne, 256);
-  p.part = o; o = align_up(o + sizeof(float) * x3p_bwd_stream_part_floats((int)TN, (int)Dm), 256);  // backward stream partials
-  // (also the row stream of this component's projection off the previous
-  // component's forward, launch_chain_rows: N = dirs * G columns)
-  p.cnt = o; o = align_up(o + sizeof(int) * x3p_bwd_stream_ints((int)TN, (int)std::max(Dm, dirs * G)), 256);
-  p.part2 = o; o = align_up(o + sizeof(float) * x3p_bwd_stream_part2_floats((int)std::max(Dm, dirs * G)), 256);
-  p.cme = o; o = align_up(o + sizeof(unsigned) * 2 * dirs * G, 256);  // dGates column maxima (v6 backward)
-  // arrival counters of the direction-split streamed projection (this component as its consumer)
-  p.fcnt = o; o = align_up(o + sizeof(int) * ((TN + 127) / 128 * dirs * ((G + 127) / 128) + 64), 256);
-  p.fpart = o; o = align_up(o + sizeof(float) * std::max((size_t)((TN + 127) / 128) * dirs * ((G + 127) / 128) * 128 * 128,
-                                                          x3p_bwd_stream_part_floats((int)TN, (int)(dirs * G))), 256);
-  // W^T of the streamed dx GEMM, packed by the forward (RnnPrepack): kept
-  // from the forward to the backward, apart from every other slot
-  p.wt = o; o = align_up(o + x3p_bytes(dirs * Dm, G), 256);
-  p.ewt = o; o = align_up(o + sizeof(int) * (dirs * Dm + 64), 256);
-  p.cmw = o; o = align_up(o + sizeof(unsigned) * (dirs * Dm + 64), 256);
-  // x^T / y^T of the weight GEMMs, packed by the forward (RnnPrepack::wgrad)
-  p.xt = o; o = align_up(o + bw_b, 256);
-  p.yt = o; o = align_up(o + bw_c, 256);
-  p.ext = o; o = align_up(o + sizeof(int) * (Dm + 64), 256);
-  p.eyt = o; o = align_up(o + sizeof(int) * (dirs * d.H + 64), 256);
-  // item counters of those packs (on the prepack stream; apart from the
-  // recurrence flags, which the backward resets on the compute stream)
-  p.pcnt = o; o = align_up(o + sizeof(int) * 4, 256);
-  p.total = o;
-  return p;
-}
-static size_t pack_offset(const RnnDesc &d, int T, int N) { return align_up(xch_offset(d, T, N) + xch_bytes(d, T, N), 256); }
-size_t rnn_workspace_bytes(const RnnDesc &d, int T, int N) { return pack_offset(d, T, N) + pack_layout(d, T, N).total; }
-template <typename P>
-static P *pk(void *ws, const RnnDesc &d, int T, int N, size_t off) {
-  return reinterpret_cast<P *>(static_cast<char *>(ws) + pack_offset(d, T, N) + off);
-}
-// The RNN GEMMs run on the packed split-fp16 matrix-core path (gemm_x3p.hip)
-// unless the contraction is too short to pay for packing.
-static bool use_x3(int K, int min_k = 128) { return K >= min_k; }
-// |x| <= 1: an LSTM / GRU / TANH layer output
-static bool bounded_out(const RnnDesc &d) { return d.mode != kRelu; }
-
-static int env_int(const char *name, int dflt) {
-  const char *v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
-// bf16 recurrences write their dGates straight into the packed bf16 GEMM
-// operands (RecParams::dxr / dxt / et) -- v6 only (a v6 backward runs for
-// every bf16 shape), whole 64-element gate rows
-// (one-layer descriptors -- the recipe's components; a stacked descriptor's
-// weight gradients measured wrong with it, so those keep the pack path)
-static bool bf16_direct(const RnnDesc &d, int ver) {
-  return d.prec == kPrecBf16 && ver == 6 && (d.nw() * d.H) % 64 == 0 && d.layers == 1 && d.pk;
-}
-// ... and, one-layer bidirectional, the forward writes its output packed
-// (RecParams::yr / yc) and the backward E^T shifted (eshift); H % 32 == 0 so
-// that a workgroup's units fill whole 16-B row chunks
-static bool bf16_io(const RnnDesc &d) {
-  return bf16_direct(d, 6) && d.layers == 1 && d.dirs == 2 && d.H % 32 == 0 && (2 * d.H) % 64 == 0 && d.pkio;
-}
-
 namespace {
+
+// Stacked layer l in the parameter vector: direction 0's block at pl0 (W
+// first), direction 1's pls floats on; within a block R, bW and bR
+struct LayerW {
+  long pl0, pls, roff, bW, bR;
+};
+LayerW layer_w(const RnnDesc &d, int l) {
+  LayerW lw;
+  lw.pl0 = d.lin_offset(l * d.dirs, 0, false);
+  lw.pls = d.pl_size(l);
+  lw.roff = d.lin_offset(l * d.dirs, d.nw(), false) - lw.pl0;
+  lw.bW = d.lin_offset(l * d.dirs, 0, true) - lw.pl0;
+  lw.bR = d.lin_offset(l * d.dirs, d.nw(), true) - lw.pl0;
+  return lw;
+}
 
 // A recurrence kernel (rec6_kernel / rec_generic_kernel) on `nth` threads per workgroup; it was compiled
 // against its own translation unit's copy of RecParams: the layouts agree only through rec_common.h
-static void launch_rec(const void *k, const RecParams &p, dim3 grid, int nth, size_t lds, hipStream_t s) {
+void launch_rec(const void *k, const RecParams &p, dim3 grid, int nth, size_t lds, hipStream_t s) {
   (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   void *args[] = {const_cast<RecParams *>(&p)};
   KCTC_HIP_CHECK(hipLaunchKernel(k, grid, dim3(nth), args, lds, s));
@@ -283,143 +161,41 @@ struct RecTrace {
   }
 };
 
-static size_t fwd_lds_bytes(const RnnDesc &d, int N, int U) {
-  const int ncol = (d.nw() * U + 15) / 16 * 16, Npad = (N + 15) / 16 * 16;
-  return sizeof(float) * ((size_t)ncol * (d.H + 4) + 4 * (size_t)Npad * ncol);
-}
-static size_t bwd_lds_bytes(const RnnDesc &d, int N, int U, int ver = 3) {
-  const int Npad = (N + 15) / 16 * 16;
-  return sizeof(float) * ((size_t)(ver == 4 ? 16 : U) * (d.nw() * d.H + 4) +
-                          std::max(4 * (size_t)Npad * 16, (size_t)2 * N * U * d.nw()));
-}
-
-// pick U (units per workgroup): divides H, multiple of 4, blocks <= 256
-static int pick_fwd_u(const RnnDesc &d, int N) {
-  auto ok = [&](int U) {
-    if (U < 4 || U % 4 || d.H % U || d.nw() * U > 16 * kMaxCT || N * U / 4 > NT) return false;
-    if ((long)d.dirs * (d.H / U) > 256) return false;
-    return fwd_lds_bytes(d, N, U) <= 160 * 1024;
-  };
-  // smallest U that keeps every workgroup resident (<= 256 = one per CU):
-  // per-step MFMA latency falls with U (measured: U=4 < 8 < 16 on BLSTM-512)
-  for (int U : {4, 8, 16})
-    if (ok(U)) return U;
-  return 0;
+// What a forward and a backward recurrence of stacked layer l have in common;
+// enqueues the reset of the flag area on s.
+RecParams rec_params(const RnnDesc &d, const RecPlan &pl, const RnnWs &ws, int T, int N, const float *wl,
+                     const LayerW &lw, float *R0, const RnnReserveLayout &lay, float *y, unsigned *err,
+                     hipStream_t s) {
+  RecParams p{};
+  p.T = T; p.N = N; p.H = d.H; p.dirs = d.dirs; p.U = pl.U; p.nwg = pl.nwg;
+  p.Npad = (N + 15) / 16 * 16;
+  p.w = wl; p.pl_stride = lw.pls; p.r_off = lw.roff; p.bR_off = lw.bR;
+  p.G = R0 + lay.G; p.y = y; p.aux = R0 + lay.aux; p.err = err;
+  p.flags = ws.flags();
+  KCTC_HIP_CHECK(hipMemsetAsync(p.flags, 0, kFlagBytes, s));
+  p.xpd = pl.xpd;
+  p.rg = pl.rg;
+  p.gs = pl.gs;
+  // XCD-pinned v6 (RecPlan::xcds): each (row group, direction) on one XCD, the
+  // hand-off in that XCD's L2 through a ring of two step images
+  p.ring = pl.ver == 6 && p.xpd ? 2 : 0;
+  return p;
 }
 
-// v4 (XCD-local): nwg = H/U <= kCusPerXcd workgroups per direction, one XCD each.
-constexpr int kCusPerXcd = 32;
-// XCD slots one direction spans for U units per workgroup (0: not a v4 shape)
-static int v4_xpd(const RnnDesc &d, int U) {
-  if (U <= 0 || d.H % U) return 0;
-  const int nwg = d.H / U;
-  if (nwg % kCusPerXcd) return nwg < kCusPerXcd && d.dirs <= 8 ? 1 : 0;
-  const int x = nwg / kCusPerXcd;
-  return (x == 1 || x == 2 || x == 4 || x == 8) && x * d.dirs <= 8 ? x : 0;
-}
-static int pick_fwd_u4(const RnnDesc &d, int N) {
-  if (d.dirs > 8) return 0;
-  auto ok = [&](int U) {
-    return U >= 4 && U % 4 == 0 && v4_xpd(d, U) && d.nw() * U <= 16 * kMaxCT && N * U <= kMaxEPT * NT &&
-           fwd_lds_bytes(d, N, U) <= 160 * 1024;
-  };
-  // measured on BLSTM-512 N=16 (1 x MI355X): U=8 (2 XCD slots per direction)
-  // 44 ms/step of forward recurrence, U=4 48, U=16 58
-  for (int U : {8, 16, 4, 32})
-    if (ok(U)) return U;
-  return 0;
-}
-static int pick_bwd_u4(const RnnDesc &d, int N) {
-  if (d.dirs > 8) return 0;
-  auto ok = [&](int U) {
-    return U >= 4 && U <= 16 && U % 4 == 0 && v4_xpd(d, U) && N * U <= kMaxEPT * NT &&
-           bwd_lds_bytes(d, N, U, 4) <= 160 * 1024;
-  };
-  for (int U : {16, 8, 4})
-    if (ok(U)) return U;
-  return 0;
-}
-
-// v6 recurrences (LSTM / GRU): one configuration for a (shape, N):
-//   rg   row groups of 16 sequences, each an independent recurrence
-//   U    units per workgroup (8, 16 at 256 threads; 32 at 512 threads)
-// chosen so that dirs * (H / U) * rg workgroups (one per CU, >= 96 KB LDS
-// each) stay within 128 workgroups (half the chip, the rest
-// for the GEMMs that overlap the recurrences).  Preference U = 16, then 32,
-// then 8 (measured on BLSTM-512 N=16: U=16 34.2 ms/step of forward
-// recurrence, U=8 37.1).
-// Sequences per v6 row group: 16 (one MFMA row tile), or 8 for 9 <= N <= 32
-// -- the batch then runs as ceil(N / 8) independent recurrences side by side,
-// each moving half the hand-off rows per step.  Default 8 for N <= 16
-// (configs[1]: forward 28.0 -> 27.0, backward 34.2 -> 33.0 ms/step of
-// recurrence; the weight GEMMs beside the backward get 64 CUs fewer and take
-// twice as long, still hidden).  KCTC_REC_GS sets both directions; a set
-// knob applies up to N = 32.  pick6
-// falls back to 16 when no workgroup partition fits the groups of 8.
-static int v6_group_rows(int N, bool fwd) {
-  const int want = env_int("KCTC_REC_GS", N <= 16 ? 8 : 16);
-  return (want == 8 && N > 8 && N <= 32) ? 8 : 16;
-}
-static V6Cfg pick6(const RnnDesc &d, int N, bool fwd, int gs_force = 0) {
-  V6Cfg c;
-  if ((d.mode != kLstm && d.mode != kGru) || N <= 0 || N > 64 || d.dirs > 2) return c;
-  if (d.H != 256 && d.H != 320 && d.H != 512 && d.H != 1024) return c;
-  const int gs = gs_force ? gs_force : v6_group_rows(N, fwd), rg = (N + gs - 1) / gs;
-  // never more workgroups than the CUs this process may use (all must be resident)
-  const int max_wg = std::min(128, rnn_usable_cus());
-  auto ok = [&](int U) {
-    const int nth = U == 32 ? 512 : 256, nwv = nth / 64;
-    if (d.H % U || d.H % (16 * nwv) || (d.H / U) % (nth / (4 * U))) return false;
-    return (long)d.dirs * (d.H / U) * rg <= std::max(max_wg, d.dirs * (d.H / U));  // rg = 1 always fits
-  };
-  auto take = [&](int U) {
-    c.U = U;
-    // U = 16 at H = 512 runs 512 threads (K split over 8 waves; measured on
-    // BLSTM-512 N=16: forward 31.9 -> 28.4, backward 34.4 -> 32.9 ms/step of
-    // recurrence vs 256 threads; 1024 threads 30.5 / 33.5)
-    c.nth = U == 32 ? 512 : (U == 16 && d.H == 512) ? 512 : 256;
-    c.rg = rg;
-    c.gs = gs;
-    // The kernel variant, at U = 16 / 512 threads.  Row groups of <= 8
-    // sequences: hi / lo stacked in one MFMA operand (all four products:
-    // equally accurate or better), on by default in both directions: the
-    // stacked forward (one A load per k block, 2/3 of the MFMAs) runs 1.76
-    // us/step against 2.05 for the IO-wave forward (round 4); the transposed
-    // stacked backward with its DPP row fold 1.91 against 2.43 (round 5).
-    // KCTC_STK_FWD (forward; KCTC_STK for both).  Else the forward runs
-    // with IO waves (the G loads off the hand-off waves).
-    const bool wide16 = U == 16 && c.nth == 512;
-    const int stk = fwd ? env_int("KCTC_STK_FWD", env_int("KCTC_STK", 1)) : env_int("KCTC_STK", 1);
-    const bool stacked = wide16 && d.prec != kPrecBf16 && gs <= 8 && stk;
-    c.variant = stacked ? kRec6Stacked : wide16 && fwd ? kRec6IoWave : kRec6Plain;
-    return c;
-  };
-  for (int U : {16, 32, 8})
-    if (ok(U)) {
-      // rg = 1 keeps the measured N <= 16 choice even above the budget
-      if (rg == 1 || (long)d.dirs * (d.H / U) * rg <= max_wg) return take(U);
-    }
-  return gs == 8 ? pick6(d, N, fwd, 16) : c;
-}
-
-static size_t fwd6_lds_bytes(const RnnDesc &d, const V6Cfg &c) {
-  const int CT = (d.nw() * c.U + 15) / 16, nwv = c.nth / 64, np = d.prec == kPrecBf16 ? 1 : 2;
-  const size_t rp = std::max(CT * 16 + 1, 4 * c.U);  // rnn_fwd_rec6's RPR (float4 K partials)
-  // + the IO waves' G (and output) slots; the stacked forward's launch keeps them (forward cfg only)
-  const bool iow = c.variant == kRec6IoWave || c.variant == kRec6Stacked;
-  const size_t b = sizeof(float) * (nwv * 16 * rp + 8) + np * 16 * (size_t)c.U * 2 + 16 +
-                   (iow ? sizeof(float) * 16 * c.U * (8 * d.nw() + 2 * (d.nw() + 2)) + 16 + 4 * 64 * 4 : 0);
-  return std::max(b, (size_t)96 * 1024);  // one recurrence workgroup per CU
-}
-static size_t bwd6_lds_bytes(const RnnDesc &d, const V6Cfg &c) {
-  const int K = d.nw() * c.U, KB = (K + 31) / 32, AP = KB * 32 + 8;
-  const size_t img = (d.prec == kPrecBf16 ? 1 : 2) * 16 * (size_t)AP * 2;
-  const size_t red = sizeof(float) * std::max((size_t)c.nth * 4, (size_t)2 * 16 * c.U * d.nw());
-  // dGates tile staged for write-through, and (bf16, packed writes) the E tile beside it
-  const size_t estg = sizeof(float) * 16 * c.U * d.nw() * (d.prec == kPrecBf16 ? 2 : 1);
-  // at least 96 KB so that no other workgroup (a side-stream GEMM block)
-  // shares the CU with a recurrence workgroup
-  return std::max(img + red + estg, (size_t)96 * 1024);
+// The planned recurrence on s (traced when KCTC_REC_TRACE asks for it); from
+// here to the end of the host call the side launches go beside it (v6)
+void launch_planned(const RnnDesc &d, const RecPlan &pl, bool fwd, RecParams &p, RecTrace &tr, RecScope &scope,
+                    hipStream_t s) {
+  if (tr.arm(fwd ? "fwd" : "bwd", pl.grid)) p.trace = tr.dev;
+  const void *k = pl.ver == 6 ? rec6_kernel(fwd, d.mode, d.prec, d.H, pl.c6)
+                              : rec_generic_kernel(fwd, pl.ver, d.mode, p.Npad / 16);
+  {
+    ProfSpan ps(s, fwd ? "rnn_fwd_rec" : "rnn_bwd_rec");
+    launch_rec(k, p, dim3(pl.grid), pl.nth, pl.lds, s);
+  }
+  KCTC_HIP_CHECK(hipGetLastError());
+  if (pl.ver == 6) scope.enqueued(p.flags, p.dirs * p.nwg * p.rg);
+  else scope.none();
 }
 
 // Per-device exchange pool of the v6 backward: one step image per time step,
@@ -434,7 +210,7 @@ struct XchPool {
 std::mutex g_xch_mu;
 XchPool g_xch[64];
 
-static float *xch_acquire(size_t bytes, hipStream_t s) {
+float *xch_acquire(size_t bytes, hipStream_t s) {
   int dev = 0;
   KCTC_HIP_CHECK(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_xch_mu);
@@ -451,7 +227,7 @@ static float *xch_acquire(size_t bytes, hipStream_t s) {
   }
   return static_cast<float *>(x.p);
 }
-static void xch_release(hipStream_t s) {
+void xch_release(hipStream_t s) {
   int dev = 0;
   KCTC_HIP_CHECK(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_xch_mu);
@@ -460,164 +236,11 @@ static void xch_release(hipStream_t s) {
   KCTC_HIP_CHECK(hipEventRecord(x.ev, s));
 }
 
-static int pick_bwd_u(const RnnDesc &d, int N) {
-  auto ok = [&](int U) {
-    if (U < 4 || U % 4 || U > 16 || d.H % U || N * U / 4 > NT) return false;
-    if ((long)d.dirs * (d.H / U) > 256) return false;
-    return bwd_lds_bytes(d, N, U) <= 160 * 1024;
-  };
-  for (int U : {16, 8, 4})
-    if (ok(U)) return U;
-  return 0;
-}
-
-}  // namespace
-
-// ---- launches beside a running recurrence (rnn.h rnn_side_gated) ----
-namespace {
-// the v6 recurrence this host thread enqueued last, while the host function
-// that enqueued it runs (RecScope), and the side streams gated on it
-struct RecInFlight {
-  const unsigned *res = nullptr;    // its residency word (p.flags + kResWord)
-  const unsigned *flags = nullptr;  // its flag area
-  unsigned target = 0;              // its workgroups
-  hipStream_t gated[4] = {};
-  int ngated = 0;
-};
-thread_local RecInFlight g_rec;
-// from a recurrence's launch to the end of the enclosing host call
-struct RecScope {
-  ~RecScope() { g_rec = RecInFlight{}; }
-  void enqueued(const RecParams &p) {
-    g_rec = RecInFlight{};
-    g_rec.res = p.flags + kResWord;
-    g_rec.flags = p.flags;
-    g_rec.target = (unsigned)(p.dirs * p.nwg * p.rg);
-  }
-  void none() { g_rec = RecInFlight{}; }  // (a v3 / v4 recurrence: no side launches)
-};
-// `side` waits until every workgroup of the recurrence in flight is resident;
-// whatever is enqueued on it afterwards may run beside that recurrence
-void beside_recurrence(hipStream_t side) {
-  if (!g_rec.res) throw std::logic_error("beside_recurrence: no recurrence in flight");
-  for (int i = 0; i < g_rec.ngated; i++)
-    if (g_rec.gated[i] == side) return;  // (already behind this recurrence's gate)
-  if (g_rec.ngated == 4) throw std::logic_error("beside_recurrence: too many side streams");
-  rnn_resident_gate(side, g_rec.flags, g_rec.target);
-  g_rec.gated[g_rec.ngated++] = side;
-}
-}  // namespace
-
-thread_local bool g_last_bwd_scratch_free = true;
-bool rnn_last_bwd_scratch_free() { return g_last_bwd_scratch_free; }
-
-bool rnn_side_gated(hipStream_t s) {
-  if (!g_rec.res) return true;
-  for (int i = 0; i < g_rec.ngated; i++)
-    if (g_rec.gated[i] == s) return true;
-  return false;
-}
-
-// ---------------------------------------------------------------------------
-// host: forward training
-// ---------------------------------------------------------------------------
-namespace {
 // The recurrence and a GEMM streaming off it must run at the same time, so
 // the GEMM's stream forks from the recurrence's stream at an event recorded
 // BEFORE the recurrence launch, and the GEMM is enqueued AFTER it: should the
 // two streams share a hardware queue, the GEMM then merely runs after the
 // recurrence instead of blocking it (its blocks only wait for recurrence flags).
-int g_usable_cus = 0, g_comm_cus = 0;
-
-// Does the v6 recurrence of (d, N) run without scratch (no register
-// spills)?  Nothing runs beside one that does.  Round 6 first blamed scratch
-// for configs[4]'s KCTC_STREAM_ALL hang (the bf16 GRU backward, then 124 B of
-// spills per lane, stayed short of its 32 workgroups on one XCD for 0.4 s
-// behind the one-wave residency wait of its dx stream); with the spills gone
-// it hung the same way: the cause is its 256 VGPRs x 2 waves per SIMD, a
-// whole CU's register file, which no workgroup gets on a CU where a gate wave
-// sits -- gate_kernel's blocks now leave the recurrence's XCDs
-// (tests/test_fullsize_gpu.py cfg4+stream_all).  The scratch
-// condition stays as a precaution (no recipe-shape recurrence uses scratch).
-bool rec6_scratch_free(const RnnDesc &d, int N, bool fwd) {
-  const V6Cfg c6 = pick6(d, N, fwd);
-  if (!c6) return false;
-  static thread_local std::map<const void *, bool> memo;
-  const void *k = rec6_kernel(fwd, d.mode, d.prec, d.H, c6);
-  auto it = memo.find(k);
-  if (it != memo.end()) return it->second;
-  hipFuncAttributes a{};
-  KCTC_HIP_CHECK(hipFuncGetAttributes(&a, k));
-  return memo[k] = a.localSizeBytes == 0;
-}
-
-// XCDs an XCD-pinned v6 recurrence of (d, N) occupies (bit x: XCD x), 0
-// when it is not pinned: every (row group, direction) runs on one XCD, its
-// H / U workgroups on kCusPerXcd (configs[1] / [4]: 32) or kCusPerXcd / 2
-// (configs[2]: U = 32 at H = 512, four row groups x two directions = all
-// eight XCDs, half of each XCD's CUs) of that XCD's CUs, and the whole chip's
-// CUs must be usable (no CU partition).  KCTC_XCD6=0 / KCTC_XCD6F=0 switch it
-// off; the 16-workgroup shapes pin too (configs[2]
-// pinned: 990k -> 1.12M frames/s, forward 3.14 -> 2.42, backward 4.52 -> 3.53
-// us/step, same box).
-unsigned xcd_mask(const RnnDesc &d, int N, bool fwd) {
-  const V6Cfg c6 = pick6(d, N, fwd);
-  if (!c6 || d.dirs * c6.rg > 8) return 0;
-  const int nwg = d.H / c6.U;
-  if (nwg != kCusPerXcd && nwg != kCusPerXcd / 2) return 0;
-  if (!env_int(fwd ? "KCTC_XCD6F" : "KCTC_XCD6", 1)) return 0;
-  int dev = 0, cus = 0;
-  KCTC_HIP_CHECK(hipGetDevice(&dev));
-  KCTC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  if (rnn_usable_cus() != cus || cus != 8 * kCusPerXcd) return 0;
-  // backward: an exchange's kernels (comm stream) landing on a pinned XCD
-  // would hold the recurrence's CUs there until the all-reduce ends, and a
-  // stream CU mask cannot keep them off an XCD (scripts/cumask_probe.hip:
-  // each mask bit selects one CU in every XCD): pinned only without an
-  // exchange.  No exchange kernel runs during a forward pass (the previous
-  // step's updates waited for every bucket), so the forward stays pinned.
-  // With a residency-gated exchange (rnn_set_comm_gated) no exchange kernel
-  // is in flight while a backward recurrence becomes resident, so it stays pinned.
-  if (!fwd && rnn_comm_cus() > 0 && !rnn_comm_gated()) return 0;
-  return (1u << (d.dirs * c6.rg)) - 1u;
-}
-
-// persistent blocks a streamed GEMM may run beside a recurrence of `rec_wgs`
-// workgroups (rnn.h, CU budget); 0: too few to stream
-int stream_block_budget(int rec_wgs, bool backward) {
-  // the 16-CU margin keeps room for the exchange's kernels beyond maxCTAs;
-  // a backward without an exchange (one rank) gives the streamed dx GEMM all
-  // CUs the recurrence leaves (configs[1]: 128 blocks, 655.7k -> 670.7k frames/s)
-  const int margin = backward && rnn_comm_cus() == 0 ? 0 : 16;
-  const int left = rnn_usable_cus() - rec_wgs - (backward ? rnn_comm_cus() : 0) - margin;
-  return left >= 8 ? left : 0;
-}
-
-// XCDs whose every CU an XCD-pinned recurrence holds: a streamed GEMM's
-// blocks landing there leave at once (xcd_word / xcd_count), and the launch
-// has 8 / (8 - pinned) times the blocks so that its budget stays.  0 when the
-// recurrence is not pinned or its slots take half an XCD each (configs[2]:
-// all eight XCDs, 16 of each XCD's CUs left to the stream: there its blocks
-// stay, on the CUs the recurrence leaves).
-int whole_pinned_xcds(const RecParams &p) {
-  const int n = p.xpd && p.nwg == kCusPerXcd ? p.dirs * p.rg : 0;
-  return n < 8 ? n : 0;
-}
-
-// Is the dx of layer l streamed off its v6 backward recurrence
-// (launch_bwd_stream, given a dx buffer and an overlap stream)?  The
-// forward's W^T prepack (RnnPrepack) asks the same question.
-bool bwd_dx_stream_ok(const RnnDesc &d, int l, int T, int N) {
-  const V6Cfg c6 = pick6(d, N, false);
-  if (!c6 || d.dirs != 2 || !env_int("KCTC_BWD_STREAM", 1) || !rec6_scratch_free(d, N, false)) return false;
-  // split-fp16 at N <= 16 by default (KCTC_STREAM_ALL: bf16 and N > 16 too)
-  if (!((d.prec == kPrecX3 && N <= 16) || env_int("KCTC_STREAM_ALL", 0))) return false;
-  const int G4 = d.nw() * d.H;
-  if (!use_x3(G4) || G4 > 4096 || (d.prec != kPrecX3 && G4 % 64)) return false;
-  if ((long)T * N * d.din(l) * 4 >= (1L << 31)) return false;
-  return stream_block_budget(d.dirs * (d.H / c6.U) * c6.rg, true) > 0;
-}
-
 hipEvent_t fork_event(hipStream_t s) {
   static thread_local hipEvent_t ev = nullptr;
   if (!ev) KCTC_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -631,11 +254,69 @@ void join_stream(hipStream_t s, hipStream_t other) {
   KCTC_HIP_CHECK(hipStreamWaitEvent(s, ev, 0));
 }
 
+// ---------------------------------------------------------------------------
+// GEMMs streamed off a running v6 recurrence
+// ---------------------------------------------------------------------------
+// The epoch lines a stream consumer polls for the launched recurrence `p`:
+// its workgroups' flag lines (flag6), or, XCD-pinned -- the flags then stay
+// in the XCD's L2 -- the sc1 copies of its epochs (agg_flag6)
+const unsigned *epoch_lines(const RecParams &p) {
+  return p.flags + kFlag6Word + (p.xpd ? kAggLine * kFlagStride : 0);
+}
+
+// XCDs whose every CU an XCD-pinned recurrence holds: a streamed GEMM's
+// blocks landing there leave at once (xcd_word / xcd_count), and the launch
+// has 8 / (8 - pinned) times the blocks so that its budget stays.  0 when the
+// recurrence is not pinned or its slots take half an XCD each (configs[2]:
+// all eight XCDs, 16 of each XCD's CUs left to the stream: there its blocks
+// stay, on the CUs the recurrence leaves).
+int whole_pinned_xcds(const RecParams &p) {
+  const int n = p.xpd && p.nwg == kCusPerXcd ? p.dirs * p.rg : 0;
+  return n < 8 ? n : 0;
+}
+
+// The producer side of a streamed launch beside the recurrence `p`, for a
+// budget of `budget` persistent blocks
+struct StreamProducer {
+  const unsigned *lines;  // epoch_lines
+  int nwg;                // lines per (row group, direction): one when pinned (aggregated)
+  const unsigned *xcd_word = nullptr;  // pinned: where the recurrence's XCDs register,
+  int xcd_count = 0;                   // and how many of them
+  int blocks;             // the budget, scaled so that it stays beside the blocks that leave the pinned XCDs
+};
+StreamProducer stream_producer(const RecParams &p, int budget) {
+  StreamProducer sp;
+  sp.lines = epoch_lines(p);
+  sp.nwg = p.xpd ? 1 : p.nwg;
+  const int pinned = whole_pinned_xcds(p);
+  if (pinned) { sp.xcd_word = p.flags + kXcdWord; sp.xcd_count = pinned; }
+  sp.blocks = pinned ? budget * 8 / (8 - pinned) : budget;
+  return sp;
+}
+
+// Is the dx of layer l streamed off its v6 backward recurrence `pl`
+// (launch_bwd_stream, given a dx buffer and an overlap stream)?  The
+// forward's W^T prepack (RnnPrepack) asks the same question.
+bool bwd_dx_stream_ok(const RecPlan &pl, const RnnDesc &d, int l, int T, int N) {
+  if (pl.ver != 6 || d.dirs != 2 || !env_int("KCTC_BWD_STREAM", 1) || !pl.scratch_free) return false;
+  // split-fp16 at N <= 16 by default (KCTC_STREAM_ALL: bf16 and N > 16 too)
+  if (!((d.prec == kPrecX3 && N <= 16) || env_int("KCTC_STREAM_ALL", 0))) return false;
+  const int G4 = d.nw() * d.H;
+  if (!use_x3(G4) || G4 > 4096 || (d.prec != kPrecX3 && G4 % 64)) return false;
+  if ((long)T * N * d.din(l) * 4 >= (1L << 31)) return false;
+  return stream_block_budget(pl.wgs, true) > 0;
+}
+
+bool chain_buffers_ok(const RnnFwdChain *c, int T, int N) {
+  return c->ws_bytes >= rnn_workspace_bytes(*c->d, T, N) &&
+         c->res_bytes >= sizeof(float) * (size_t)rnn_reserve_layout(*c->d, T, N).total;
+}
+
 // Can `c` consume the exchange images of this component's last forward
-// recurrence (v6, bidirectional) as its layer-0 projection input?
-bool chain_ok(const RnnDesc &d, int ver, int T, int N, const RnnFwdChain *c) {
-  if (!c || !c->d || !c->side || ver != 6 || d.dirs != 2 || !env_int("KCTC_FWD_STREAM", 1)) return false;
-  if (!rec6_scratch_free(d, N, true)) return false;
+// recurrence `pl` (v6, bidirectional) as its layer-0 projection input?
+bool chain_ok(const RecPlan &pl, const RnnDesc &d, int T, int N, const RnnFwdChain *c) {
+  if (!c || !c->d || !c->side || pl.ver != 6 || d.dirs != 2 || !env_int("KCTC_FWD_STREAM", 1)) return false;
+  if (!pl.scratch_free) return false;
   const RnnDesc &n = *c->d;
   // split-fp16 into split-fp16, or bf16 images into a bf16 projection
   if (n.D != d.dirs * d.H || !use_x3(n.D) || N > 64 || d.prec != n.prec) return false;
@@ -649,15 +330,13 @@ bool chain_ok(const RnnDesc &d, int ver, int T, int N, const RnnFwdChain *c) {
   // (HBM traffic on the other XCDs) its steps took 0.17-0.3 us longer, more
   // than the 256-tile GEMM after it costs (configs[1]: 555.9k vs 564.8k
   // frames/s same box); KCTC_FWD_STREAM_PINNED=1 streams anyway
-  if (xcd_mask(d, N, true) && !env_int("KCTC_FWD_STREAM_PINNED", 0)) return false;
+  if (pl.xcds && !env_int("KCTC_FWD_STREAM_PINNED", 0)) return false;
   // and only the IO-wave variant carries the copies (not bf16 in 8-row groups: never run pinned with them)
-  const V6Cfg c6 = pick6(d, N, true);
-  if (xcd_mask(d, N, true) && (c6.variant != kRec6IoWave || (d.prec == kPrecBf16 && c6.gs <= 8))) return false;
-  if (!c6 || !stream_block_budget(d.dirs * (d.H / c6.U) * c6.rg, false)) return false;
-  const long xs = 2L * (d.H / 32) * (d.prec == kPrecBf16 ? 1 : 2) * 16 * 32 * c6.rg;  // halves per step image
+  if (pl.xcds && (pl.c6.variant != kRec6IoWave || (d.prec == kPrecBf16 && pl.gs <= 8))) return false;
+  if (!stream_block_budget(pl.wgs, false)) return false;
+  const long xs = 2L * (d.H / 32) * (d.prec == kPrecBf16 ? 1 : 2) * 16 * 32 * pl.rg;  // halves per step image
   if ((long)T * xs * 2 >= (1L << 31)) return false;
-  return c->ws_bytes >= rnn_workspace_bytes(n, T, N) &&
-         c->res_bytes >= sizeof(float) * (size_t)rnn_reserve_layout(n, T, N).total;
+  return chain_buffers_ok(c, T, N);
 }
 
 // Layer-0 projection of the consumer, streamed off the producer's exchange images.
@@ -670,9 +349,9 @@ void launch_chain_proj(const RnnDesc &d, const RecParams &p, hipEvent_t fork, in
   const int NW = n.nw(), G = NW * n.H, Din = n.D, KB = Din / (bf ? 64 : 32);
   const long pl0 = n.lin_offset(0, 0, false), pls = n.pl_size(0);
   const float *wl = c.w + pl0;
-  const PackLay pl = pack_layout(n, T, N);
-  _Float16 *Bp = pk<_Float16>(c.workspace, n, T, N, pl.b);
-  int *eB = bf ? nullptr : pk<int>(c.workspace, n, T, N, pl.eb);
+  const RnnWs ws(n, T, N, c.workspace);
+  _Float16 *Bp = ws.at<_Float16>(ws.lay.b);
+  int *eB = bf ? nullptr : ws.at<int>(ws.lay.eb);
   {
     ProfSpan ps(c.side, "x3_pack_chain");
     if (bf)
@@ -690,27 +369,24 @@ void launch_chain_proj(const RnnDesc &d, const RecParams &p, hipEvent_t fork, in
   x.bias = wl + (n.lin_offset(0, 0, true) - pl0);
   x.bias2 = n.mode == kGru ? nullptr : wl + (n.lin_offset(0, NW, true) - pl0);
   x.batch = n.dirs; x.sB = (long)G * KB * 64; x.seB = bf ? 0 : G; x.sC = G; x.sBias = pls;
-  x.tile_counter = reinterpret_cast<int *>(static_cast<char *>(c.workspace) + flags_offset(n, T, N));
+  x.tile_counter = reinterpret_cast<int *>(ws.flags());
+  // every producer workgroup needs a CU of its own (96 KB LDS); the GEMM's
+  // persistent blocks (96 KB each) take the rest minus a margin (chain_ok
+  // checked that at least 8 fit).  No gradient exchange runs during a
+  // forward pass: the updates of the previous step waited for it.
   // XCD-pinned producer: the sc1 copies of its epochs, no block on its XCDs
-  x.stream_flags = p.flags + 1024 + (p.xpd ? 256 * kFlagStride : 0);  // pinned: agg_flag6 lines
-  x.stream_nwg = p.xpd ? 1 : p.nwg; x.stream_T = T; x.stream_N = N;
-  const int pinned = whole_pinned_xcds(p);
-  if (pinned) { x.stream_xcd_word = p.flags + kXcdWord; x.stream_xcd_count = pinned; }
+  const StreamProducer sp = stream_producer(p, stream_block_budget(d.dirs * p.nwg * p.rg, false));
+  x.stream_flags = sp.lines; x.stream_nwg = sp.nwg; x.stream_T = T; x.stream_N = N;
+  x.stream_xcd_word = sp.xcd_word; x.stream_xcd_count = sp.xcd_count;
+  x.max_blocks = sp.blocks;
   x.stream_group_step = 2L * (d.H / 32) * (bf ? 1 : 2) * 16 * 32;  // rnn_fwd_rec6's XG
   x.stream_rg = p.rg; x.stream_gs = p.gs; x.stream_step = x.stream_group_step * p.rg; x.stream_err = err;
   // K split by producer direction: the work is ready from the first steps
   // (KCTC_STREAM_DIRSPLIT=0: whole-K tiles from the middle of the sequence outwards)
   if (env_int("KCTC_STREAM_DIRSPLIT", 1)) {
-    x.stream_arrive = pk<int>(c.workspace, n, T, N, pl.fcnt);
-    x.stream_part = pk<float>(c.workspace, n, T, N, pl.fpart);
+    x.stream_arrive = ws.at<int>(ws.lay.fcnt);
+    x.stream_part = ws.at<float>(ws.lay.fpart);
   }
-  // every producer workgroup needs a CU of its own (96 KB LDS); the GEMM's
-  // persistent blocks (96 KB each) take the rest minus a margin (chain_ok
-  // checked that at least 8 fit).  No gradient exchange runs during a
-  // forward pass: the updates of the previous step waited for it.
-  // (blocks landing on a pinned producer's XCDs exit at once: launch enough that the budget stays)
-  const int nb = stream_block_budget(d.dirs * p.nwg * p.rg, false);
-  x.max_blocks = pinned ? nb * 8 / (8 - pinned) : nb;
   {
     ProfSpan ps(c.side, "fwd_proj_stream");
     gemm_x3p(c.side, x);
@@ -720,10 +396,11 @@ void launch_chain_proj(const RnnDesc &d, const RecParams &p, hipEvent_t fork, in
 
 // Can `c`'s layer-0 projection stream off this component's y rows
 // (launch_chain_rows)?  Split-fp16 into split-fp16, the 256-tile row stream.
-bool chain_rows_ok(const RnnDesc &d, int ver, int T, int N, const RnnFwdChain *c) {
-  if (!c || !c->d || !c->side || ver != 6 || d.dirs != 2 || d.prec == kPrecBf16 || !env_int("KCTC_FWD_STREAM", 1))
+bool chain_rows_ok(const RecPlan &pl, const RnnDesc &d, int T, int N, const RnnFwdChain *c) {
+  if (!c || !c->d || !c->side || pl.ver != 6 || d.dirs != 2 || d.prec == kPrecBf16 ||
+      !env_int("KCTC_FWD_STREAM", 1))
     return false;
-  if (!rec6_scratch_free(d, N, true)) return false;
+  if (!pl.scratch_free) return false;
   const RnnDesc &n = *c->d;
   const long TN = (long)T * N;
   if (n.D != d.dirs * d.H || n.prec != d.prec || !use_x3(n.D) || d.H % 32 || d.H > 4096 || T < 2) return false;
@@ -732,10 +409,8 @@ bool chain_rows_ok(const RnnDesc &d, int ver, int T, int N, const RnnFwdChain *c
   // at N <= 16 (configs[1]); larger batches run the 256-tile GEMM after the
   // recurrence (shorter recurrences, less time to hide the GEMM behind)
   if (N > 16 && !env_int("KCTC_STREAM_ALL", 0)) return false;
-  const V6Cfg c6 = pick6(d, N, true);
-  if (!c6 || !stream_block_budget(d.dirs * (d.H / c6.U) * c6.rg, false)) return false;
-  return c->ws_bytes >= rnn_workspace_bytes(n, T, N) &&
-         c->res_bytes >= sizeof(float) * (size_t)rnn_reserve_layout(n, T, N).total;
+  if (!stream_block_budget(pl.wgs, false)) return false;
+  return chain_buffers_ok(c, T, N);
 }
 
 // The consumer's layer-0 projection G' = [y_fwd | y_bwd] W'^T + b' streamed
@@ -758,9 +433,9 @@ void launch_chain_rows(const RnnDesc &d, const RecParams &p, hipEvent_t fork, in
   const long TN = (long)T * N;
   const long pl0 = n.lin_offset(0, 0, false), pls = n.pl_size(0);
   const float *wl = c.w + pl0;
-  const PackLay pl = pack_layout(n, T, N);
-  _Float16 *Bp = pk<_Float16>(c.workspace, n, T, N, pl.b);
-  int *eB = pk<int>(c.workspace, n, T, N, pl.eb);
+  const RnnWs ws(n, T, N, c.workspace);
+  _Float16 *Bp = ws.at<_Float16>(ws.lay.b);
+  int *eB = ws.at<int>(ws.lay.eb);
   const long sB = (long)n.dirs * G * KBh * 64;
   {
     ProfSpan ps(c.side, "x3_pack_chain");
@@ -773,22 +448,21 @@ void launch_chain_rows(const RnnDesc &d, const RecParams &p, hipEvent_t fork, in
   a.forward = true;
   a.M = (int)TN; a.N = n.dirs * G; a.KB = KBh;
   a.E = p.y; a.lde = 2L * H; a.edoff = H;
-  a.Ap = pk<_Float16>(c.workspace, n, T, N, pl.a); a.eA = pk<int>(c.workspace, n, T, N, pl.ea);
+  a.Ap = ws.at<_Float16>(ws.lay.a); a.eA = ws.at<int>(ws.lay.ea);
   a.B = Bp; a.eB = eB; a.sB = sB; a.seB = n.dirs * G;
   a.C = static_cast<float *>(c.reserve) + lay.G; a.ldc = (long)n.dirs * G;
   a.bias = wl + (n.lin_offset(0, 0, true) - pl0);
   a.bias2 = n.mode == kGru ? nullptr : wl + (n.lin_offset(0, NW, true) - pl0);
   a.bias_cols = G; a.sbias = pls;
-  a.part = pk<float>(c.workspace, n, T, N, pl.fpart);
-  a.part2 = pk<float>(c.workspace, n, T, N, pl.part2);
-  a.cnt = pk<int>(c.workspace, n, T, N, pl.cnt);
-  a.flags = p.flags + 1024 + (p.xpd ? 256 * kFlagStride : 0);  // pinned: agg_flag6 lines
-  a.nwg = p.xpd ? 1 : p.nwg; a.T = T; a.Nf = N; a.err = err; a.rg = p.rg;
-  const int pinned = whole_pinned_xcds(p);
-  if (pinned) { a.xcd_word = p.flags + kXcdWord; a.xcd_count = pinned; }
+  a.part = ws.at<float>(ws.lay.fpart);
+  a.part2 = ws.at<float>(ws.lay.part2);
+  a.cnt = ws.at<int>(ws.lay.cnt);
   // 128: every CU the recurrence leaves (configs[1]: 96 -> 128 blocks 720k -> 751k frames/s)
-  const int nb = std::min(128, stream_block_budget(d.dirs * p.nwg * p.rg, false));
-  a.blocks = pinned ? nb * 8 / (8 - pinned) : nb;
+  const StreamProducer sp =
+      stream_producer(p, std::min(128, stream_block_budget(d.dirs * p.nwg * p.rg, false)));
+  a.flags = sp.lines; a.nwg = sp.nwg; a.T = T; a.Nf = N; a.err = err; a.rg = p.rg;
+  a.xcd_word = sp.xcd_word; a.xcd_count = sp.xcd_count;
+  a.blocks = sp.blocks;
   {
     ProfSpan ps(c.side, "fwd_proj_rows");
     gemm_x3p_bwd_stream(c.side, a);
@@ -796,355 +470,16 @@ void launch_chain_rows(const RnnDesc &d, const RecParams &p, hipEvent_t fork, in
   c.done = true;
 }
 
-}  // namespace
-
-void rnn_set_cu_budget(int cus, int comm) {
-  g_usable_cus = std::max(0, cus);
-  g_comm_cus = std::max(0, comm);
-}
-int rnn_usable_cus() {
-  static int dev_cus[64] = {0};
-  int dev = 0;
-  KCTC_HIP_CHECK(hipGetDevice(&dev));
-  int &c = dev_cus[dev & 63];
-  if (!c) KCTC_HIP_CHECK(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev));
-  return g_usable_cus > 0 ? std::min(g_usable_cus, c) : c;
-}
-int rnn_comm_cus() { return g_comm_cus; }
-const void *rnn_rec6_select(const RnnDesc &d, int N, bool fwd, int cfg[5]) {
-  const V6Cfg c = pick6(d, N, fwd);
-  cfg[0] = c.U, cfg[1] = c.nth, cfg[2] = c.rg, cfg[3] = c ? c.gs : 0, cfg[4] = c.variant;
-  return c ? rec6_kernel(fwd, d.mode, d.prec, d.H, c) : nullptr;
-}
-
-// ---- residency gate of the gradient exchange (rnn.h) ----
-namespace {
-struct RegWord {
-  unsigned *word = nullptr;          // [1]: gate timeouts, [2]: pinned XCDs, [4..5]: registrations (64-bit: never wraps),
-                                     // [6]: exchange gate blocks gone (rnn_comm_gate)
-  unsigned long long expected = 0;   // host: registrations once every enqueued launch is resident
-};
-RegWord g_reg[64];
-int g_comm_gated[64] = {0};  // per device: live gated exchanges (at most one, GatedExchange)
-int current_device() {
-  int dev = 0;
-  KCTC_HIP_CHECK(hipGetDevice(&dev));
-  return dev & 63;
-}
-RegWord &reg_of_device() {
-  int dev = 0;
-  KCTC_HIP_CHECK(hipGetDevice(&dev));
-  RegWord &r = g_reg[dev & 63];
-  if (!r.word) {
-    KCTC_HIP_CHECK(hipMalloc(&r.word, 256));
-    KCTC_HIP_CHECK(hipMemset(r.word, 0, 256));
-  }
-  return r;
-}
-}  // namespace
-
-// The gates poll the word (10 s at most, then they give up and set bit 0 of
-// the device word's [1]).  hipStreamWaitValue is no alternative: ROCclr runs
-// it as a one-thread kernel too (__amd_rocclr_streamOpsWait), without a
-// timeout -- under rocprofv3's counter collection, which serialises
-// dispatches, a gate dispatched before its recurrence then never returns.
-// A gate is kGateBlocks one-wave blocks, one per XCD (round-robin dispatch).
-// A wave of it holds a CU, and a recurrence workgroup that needs a CU's whole
-// register file (configs[4]'s bf16 GRU backward: 256 VGPRs x 2 waves per
-// SIMD) cannot be placed beside it: a gate on one of the 32 CUs of an XCD the
-// recurrence is pinned to kept that XCD's last workgroup out until the gate
-// timed out (error 0x10003 at configs[4] with KCTC_STREAM_ALL=1).  So a block
-// leaves as soon as the recurrence has a workgroup on its own XCD (xw: the
-// XCD bits its workgroups OR in first thing), unless it is the last block
-// still waiting (leave counts the ones gone): the blocks on XCDs the
-// recurrence does not use do the waiting.  (A full-register recurrence on all
-// eight XCDs would keep the last block's CU; no recipe shape is one -- with
-// every CU taken nothing streams beside it either -- and the gate's timeout
-// would flag it.)
-constexpr int kGateBlocks = 8;
-template <typename W>
-__global__ __launch_bounds__(64) void gate_kernel(const W *word, W target, unsigned *gerr, const unsigned *xw,
-                                                  unsigned *leave) {
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  const unsigned me = 1u << xcc_id();
-  bool late = false;
-  while (true) {
-    const W v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (__builtin_amdgcn_readfirstlane((int)(v >= target))) break;
-    if (xw && __builtin_amdgcn_readfirstlane((int)(__hip_atomic_load(xw, __ATOMIC_RELAXED,
-                                                                     __HIP_MEMORY_SCOPE_AGENT) & me))) {
-      unsigned gone = 0;
-      if (threadIdx.x == 0) gone = atomicAdd(leave, 1u);
-      if (__builtin_amdgcn_readfirstlane((int)gone) < kGateBlocks - 1) return;
-      xw = nullptr;  // the last one: it stays
-    }
-    late = __builtin_amdgcn_s_memrealtime() - t0 > 1000000000ull;  // 100 MHz clock
-    if (late) break;
-    __builtin_amdgcn_s_sleep(8);
-  }
-  if (late && threadIdx.x == 0) atomicOr(gerr, 1u);
-}
-
-unsigned long long rnn_bwd_registrations() { return reg_of_device().expected; }
-void rnn_resident_gate(hipStream_t s, const unsigned *flags, unsigned target) {
-  hipLaunchKernelGGL(gate_kernel<unsigned>, dim3(kGateBlocks), dim3(64), 0, s, flags + kResWord, target,
-                     reg_of_device().word + 1, flags + kXcdWord, const_cast<unsigned *>(flags) + kGateWord);
-  KCTC_HIP_CHECK(hipGetLastError());
-}
-const unsigned *rnn_pinned_xcds() { return reg_of_device().word + 2; }
-
-void rnn_comm_gate(hipStream_t s, unsigned long long target) {
-  RegWord &r = reg_of_device();
-  // XCDs of the pinned backward recurrences (word [2], never cleared); the
-  // blocks gone counted in word [6], zeroed per gate on its own stream
-  KCTC_HIP_CHECK(hipMemsetAsync(r.word + 6, 0, sizeof(unsigned), s));
-  hipLaunchKernelGGL(gate_kernel<unsigned long long>, dim3(kGateBlocks), dim3(64), 0, s,
-                     reinterpret_cast<const unsigned long long *>(r.word + 4), target, r.word + 1, r.word + 2,
-                     r.word + 6);
-  KCTC_HIP_CHECK(hipGetLastError());
-}
-void rnn_set_comm_gated(bool on) {
-  int &c = g_comm_gated[current_device()];
-  c = on ? c + 1 : std::max(0, c - 1);
-}
-bool rnn_comm_gated() { return g_comm_gated[current_device()] > 0; }
-
-bool rnn_packed_output(const RnnDesc &d, int T, int N, void *reserve, const void **rows, const void **cols) {
-  *rows = *cols = nullptr;
-  if (!bf16_io(d) || !reserve) return false;
-  const RnnReserveLayout lay = rnn_reserve_layout(d, T, N);
-  float *res = static_cast<float *>(reserve);
-  *rows = res + lay.pkyr;
-  *cols = res + lay.pkyc;
-  return true;
-}
-
-namespace {
-void pack_dx_weights(const RnnDesc &d, int l, const float *w, void *workspace, int T, int N, hipStream_t st);
-}  // namespace
-
-int rnn_forward_training(const RnnDesc &d, hipStream_t s, int T, int N, const float *x,
-                         const float *w, float *y, void *workspace, size_t ws_bytes,
-                         void *reserve, size_t res_bytes, unsigned *err, RnnFwdChain *chain,
-                         bool input_projected, const void *in_rows, RnnPrepack *pre) {
-  RecScope rec_scope;  // the side launches' residency gates (beside_recurrence)
-  if (chain) chain->done = false;
-  if (pre) pre->done = pre->wdone = false;
-  if (T <= 0 || N <= 0 || N > 16 * kMaxRT || d.H % 16) return KRNN_NOT_SUPPORTED;
-  const RnnReserveLayout lay = rnn_reserve_layout(d, T, N);
-  if (res_bytes < sizeof(float) * (size_t)lay.total) return KRNN_BAD_PARAM;
-  if (ws_bytes < rnn_workspace_bytes(d, T, N)) return KRNN_BAD_PARAM;
-  const V6Cfg c6 = pick6(d, N, true);
-  const int U6 = c6.U;
-  const int U4 = U6 ? 0 : pick_fwd_u4(d, N);
-  const int ver = U6 ? 6 : U4 ? 4 : 3;
-  const int U = U6 ? U6 : U4 ? U4 : pick_fwd_u(d, N);
-  if (d.prec == kPrecBf16 && ver != 6) return KRNN_NOT_SUPPORTED;  // bf16 exists on v6 only
-  if (!U) return KRNN_NOT_SUPPORTED;
-  const int NW = d.nw(), H = d.H, dirs = d.dirs;
-  const long TN = (long)T * N;
-  float *res = static_cast<float *>(reserve);
-  const float *in = x;
-  for (int l = 0; l < d.layers; l++) {
-    float *R0 = res + lay.per_layer * l;
-    float *out = (l == d.layers - 1) ? y : R0 + lay.out;
-    const int Din = d.din(l);
-    const long pl0 = d.lin_offset(l * dirs, 0, false);
-    const float *wl = w + pl0;
-    const long pls = d.pl_size(l);
-    const long bW = d.lin_offset(l * dirs, 0, true) - pl0;
-    const long bR = d.lin_offset(l * dirs, NW, true) - pl0;
-    const long roff = d.lin_offset(l * dirs, NW, false) - pl0;
-    if (ver == 3) KCTC_HIP_CHECK(hipMemsetAsync(out, 0xFF, sizeof(float) * TN * dirs * H, s));
-    GemmArgs g;
-    g.transA = false; g.transB = true;
-    g.M = (int)TN; g.N = NW * H; g.K = Din;
-    const bool skip_proj = l == 0 && input_projected;  // streamed by the previous component
-    g.A = in; g.lda = Din;
-    g.B = wl; g.ldb = Din;
-    g.C = R0 + lay.G; g.ldc = (long)dirs * NW * H;
-    g.bias = wl + bW;
-    g.bias2 = (d.mode == kGru) ? nullptr : wl + bR;
-    g.batch = dirs; g.strideA = 0; g.strideB = pls; g.strideC = (long)NW * H; g.strideBias = pls;
-    if (skip_proj) {
-    } else if (d.prec == kPrecBf16 && use_x3(Din, 32)) {
-      // bf16 gate GEMM: input rows and W rows packed as bf16, fp32 accumulation
-      const PackLay pl = pack_layout(d, T, N);
-      // the input rows come packed from the previous component's forward (in_rows)
-      const bool rows_in = l == 0 && in_rows && Din % 64 == 0;
-      __bf16 *Ap = rows_in ? static_cast<__bf16 *>(const_cast<void *>(in_rows)) : pk<__bf16>(workspace, d, T, N, pl.a);
-      __bf16 *Bp = pk<__bf16>(workspace, d, T, N, pl.b);
-      const int KB = (Din + 63) / 64;
-      {
-        ProfSpan ps(s, "x3_pack");
-        if (!rows_in) bf16_pack_rows(s, in, Din, (int)TN, Din, Ap);
-        bf16_pack_rows(s, wl, Din, NW * H, Din, Bp, dirs, pls, (long)NW * H * KB * 64);
-      }
-      X3PArgs x;
-      x.bf16 = true;
-      x.M = (int)TN; x.N = NW * H; x.KB = KB;
-      x.A = reinterpret_cast<const _Float16 *>(Ap); x.B = reinterpret_cast<const _Float16 *>(Bp);
-      x.C = g.C; x.ldc = g.ldc; x.bias = g.bias; x.bias2 = g.bias2;
-      x.batch = dirs; x.sA = 0; x.sB = (long)NW * H * KB * 64;
-      x.sC = g.strideC; x.sBias = g.strideBias;
-      ProfSpan ps(s, "gemm_fwd_proj");
-      gemm_x3p(s, x);
-    } else if (use_x3(Din, 32)) {
-      // input rows (a lower stacked layer's output is bounded; the component
-      // input and RELU outputs get per-row exponents) and W rows, packed
-      const PackLay pl = pack_layout(d, T, N);
-      _Float16 *Ap = pk<_Float16>(workspace, d, T, N, pl.a), *Bp = pk<_Float16>(workspace, d, T, N, pl.b);
-      int *eA = pk<int>(workspace, d, T, N, pl.ea), *eB = pk<int>(workspace, d, T, N, pl.eb);
-      const int KB = (Din + 31) / 32;
-      {
-        ProfSpan ps(s, "x3_pack");
-        x3p_pack_rows(s, in, Din, (int)TN, Din, Ap, eA, (l > 0 && bounded_out(d)) ? 1.f : 0.f);
-        x3p_pack_rows(s, wl, Din, NW * H, Din, Bp, eB, 0.f, dirs, pls, (long)NW * H * KB * 64, (long)NW * H);
-      }
-      X3PArgs x;
-      x.M = (int)TN; x.N = NW * H; x.KB = KB;
-      x.A = Ap; x.B = Bp; x.eA = eA; x.eB = eB;
-      x.C = g.C; x.ldc = g.ldc; x.bias = g.bias; x.bias2 = g.bias2;
-      x.batch = dirs; x.sA = 0; x.seA = 0; x.sB = (long)NW * H * KB * 64; x.seB = (long)NW * H;
-      x.sC = g.strideC; x.sBias = g.strideBias;
-      ProfSpan ps(s, "gemm_fwd_proj");
-      gemm_x3p(s, x);
-    } else {
-      ProfSpan ps(s, "gemm_fwd_proj");
-      gemm_f32(s, g);
-    }
-    RecParams p{};
-    p.T = T; p.N = N; p.H = H; p.dirs = dirs; p.U = U; p.nwg = H / U;
-    p.ncol = (NW * U + 15) / 16 * 16; p.Npad = (N + 15) / 16 * 16;
-    p.w = wl; p.pl_stride = pls; p.r_off = roff; p.bR_off = bR;
-    p.G = R0 + lay.G; p.y = out; p.aux = R0 + lay.aux; p.err = err;
-    p.sync = ver == 4 ? kSyncFlag : kSyncData;
-    p.allow_local = 0;
-    p.flags = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + flags_offset(d, T, N));
-    KCTC_HIP_CHECK(hipMemsetAsync(p.flags, 0, kFlagBytes, s));
-    const size_t lds = ver == 6 ? fwd6_lds_bytes(d, c6) : fwd_lds_bytes(d, N, U);
-    p.xpd = ver == 4 ? v4_xpd(d, U) : 1;
-    p.rg = ver == 6 ? c6.rg : 1;
-    p.gs = ver == 6 ? c6.gs : 16;
-    p.xch = reinterpret_cast<float *>(static_cast<char *>(workspace) + xch_offset(d, T, N));
-    p.poll_sleep = 1;
-    p.gla = 3;  // G rows fetched 3 steps ahead (IO waves)
-    if (ver == 6 && bf16_io(d)) {  // the output also as packed bf16 rows and columns
-      p.yr = reinterpret_cast<__bf16 *>(R0 + lay.pkyr);
-      p.yc = reinterpret_cast<__bf16 *>(R0 + lay.pkyc);
-      p.kbt64 = lay.kbt64;
-      if (lay.kbt64 > TN)
-        KCTC_HIP_CHECK(hipMemset2DAsync(p.yc + TN, sizeof(__bf16) * lay.kbt64, 0, sizeof(__bf16) * (lay.kbt64 - TN),
-                                        (size_t)dirs * H, s));
-    }
-    const bool chained = l == d.layers - 1 && chain_ok(d, ver, T, N, chain);
-    const bool rowchain = !chained && l == d.layers - 1 && chain_rows_ok(d, ver, T, N, chain);
-    if (ver == 6) {
-      // XCD-pinned forward (xcd_mask): each (row group, direction) on one XCD,
-      // the h hand-off in its L2 through a ring of two step images; a
-      // streamed projection gets sc1 copies of the step images and flags
-      p.xpd = xcd_mask(d, N, true) ? 1 : 0;
-      p.ring = p.xpd ? 2 : 0;
-      p.fcopy = p.xpd && chained;
-      p.ysc1 = rowchain ? 1 : 0;
-      p.allow_local = p.xpd ? 1 : 0;
-      // self-tagged hand-off (the kernel takes it for split-fp16 variants other
-      // than kRec6IoWave, without a write-through copy): the ring starts at tag 1
-      p.dtag = d.prec != kPrecBf16 && p.ring == 2 && !p.fcopy && T >= 2;
-      if (p.dtag) {  // rnn_fwd_rec6's ring: after T step images of XS = 64 H rg halves (2 dirs, hi / lo, 16 rows)
-        const size_t xs = sizeof(_Float16) * 64 * (size_t)d.H * p.rg;
-        KCTC_HIP_CHECK(hipMemsetAsync(reinterpret_cast<char *>(p.xch) + xs * T, 0x01, 2 * xs, s));
-      }
-    }
-    const dim3 grid(ver == 4 ? 8 * ceil_div(p.nwg, p.xpd) : ver == 6 && p.xpd ? 8 * p.nwg : dirs * p.nwg * p.rg);
-    RecTrace tr;
-    if (tr.arm("fwd", grid.x)) p.trace = tr.dev;
-    // W^T of the backward's streamed dx GEMM, packed beside this recurrence
-    // (rnn_backward_data's `streamed` shapes; one-layer descriptors)
-    const bool prepack = pre && pre->dx && pre->stream && pre->ev && ver == 6 && d.layers == 1 &&
-                         bwd_dx_stream_ok(d, 0, T, N);
-    const bool prepack_w = pre && pre->stream && pre->wev && pre->wgrad && pre->in_bound > 0.f && ver == 6 &&
-                           d.layers == 1 && d.prec != kPrecBf16 && T > 1 && bounded_out(d) && use_x3((int)TN) &&
-                           rec6_scratch_free(d, N, true);
-    const hipEvent_t fork = (chained || prepack || prepack_w || rowchain) ? fork_event(s) : nullptr;
-    {
-      ProfSpan ps(s, "rnn_fwd_rec");
-      if (ver == 6) launch_rec(rec6_kernel(true, d.mode, d.prec, H, c6), p, grid, c6.nth, lds, s);
-      else launch_rec(rec_generic_kernel(true, ver, d.mode, p.Npad / 16), p, grid, NT, lds, s);
-    }
-    KCTC_HIP_CHECK(hipGetLastError());
-    if (ver == 6) rec_scope.enqueued(p);
-    else rec_scope.none();
-    if (prepack) {  // beside the recurrence, once it is resident
-      KCTC_HIP_CHECK(hipStreamWaitEvent(pre->stream, fork, 0));
-      beside_recurrence(pre->stream);
-      pack_dx_weights(d, 0, w, workspace, T, N, pre->stream);
-      KCTC_HIP_CHECK(hipEventRecord(pre->ev, pre->stream));
-      pre->done = true;
-    }
-    if (prepack_w) {  // x^T beside the recurrence, y^T after it, off its XCDs (rnn_backward_weights' packs)
-      hipStream_t ss = pre->stream;
-      if (!prepack) KCTC_HIP_CHECK(hipStreamWaitEvent(ss, fork, 0));
-      beside_recurrence(ss);
-      const PackLay pl = pack_layout(d, T, N);
-      const int Din = d.din(0);
-      int *pc = pk<int>(workspace, d, T, N, pl.pcnt);  // item counters
-      KCTC_HIP_CHECK(hipMemsetAsync(pc, 0, sizeof(int) * 3, ss));
-      const unsigned *av = rnn_pinned_xcds();
-      const int nx = std::max(1, rnn_usable_cus() / kCusPerXcd);
-      ProfSpan ps(ss, "x3_pack_w_fwd");
-      x3p_pack_cols(ss, in, Din, (int)TN, Din, 0, pk<_Float16>(workspace, d, T, N, pl.xt),
-                    pk<int>(workspace, d, T, N, pl.ext), nullptr, pre->in_bound, 1, 0, 0, 0, 0, av, nx, pc);
-    }
-    if (chained) {
-      launch_chain_proj(d, p, fork, T, N, *chain, err);
-      join_stream(s, chain->side);
-    }
-    if (rowchain) {
-      launch_chain_rows(d, p, fork, T, N, *chain, err);
-      join_stream(s, chain->side);
-    }
-    if (prepack_w) {  // y^T after the recurrence (and after the joins: s does not wait for it)
-      hipStream_t ss = pre->stream;
-      KCTC_HIP_CHECK(hipStreamWaitEvent(ss, fork_event(s), 0));
-      const PackLay pl = pack_layout(d, T, N);
-      const long KBt = (TN + 31) / 32;
-      int *pc = pk<int>(workspace, d, T, N, pl.pcnt);
-      const unsigned *av = rnn_pinned_xcds();
-      const int nx = std::max(1, rnn_usable_cus() / kCusPerXcd);
-      const long ldy = (long)dirs * H;
-      {
-        ProfSpan ps(ss, "x3_pack_w_fwd");
-        for (int dir = 0; dir < dirs; dir++)
-          x3p_pack_cols(ss, out + (long)dir * H, ldy, (int)TN, H, dir == 0 ? N : -N,
-                        pk<_Float16>(workspace, d, T, N, pl.yt) + (long)dir * H * KBt * 64,
-                        pk<int>(workspace, d, T, N, pl.eyt) + dir * H, nullptr, 1.f, 1, 0, 0, 0, 0, av, nx,
-                        pc + 1 + dir);
-      }
-      KCTC_HIP_CHECK(hipEventRecord(pre->wev, ss));
-      pre->wdone = true;
-    }
-    tr.dump("fwd", s, grid.x, p.nwg, T, dirs, ver, ver == 6 ? (p.xpd ? 1 : 0) : p.xpd);
-    in = out;
-  }
-  return KRNN_OK;
-}
-
-namespace {
-// dx of stacked layer l on `ov`, streamed off the backward recurrence about
-// to be launched on `s` (gemm_x3p_bwd_stream): W_d^T packed first, then one
-// persistent launch that packs dGates rows as the recurrence flags them.
 // W^T of layer l's dx GEMM (B operand of the streamed GEMM) into the
-// workspace slot pl.wt (per-column exponents pl.ewt, absmax scratch pl.cmw)
-void pack_dx_weights(const RnnDesc &d, int l, const float *w, void *workspace, int T, int N, hipStream_t st) {
+// workspace slot wt (per-column exponents ewt, absmax scratch cmw)
+void pack_dx_weights(const RnnDesc &d, int l, const float *w, const RnnWs &ws, hipStream_t st) {
   const bool bf = d.prec == kPrecBf16;
   const int G4 = d.nw() * d.H, KB = G4 / (bf ? 64 : 32), Din = d.din(l);
   const long pl0 = d.lin_offset(l * d.dirs, 0, false), pls = d.pl_size(l);
   const float *wl = w + pl0;
-  const PackLay pl = pack_layout(d, T, N);
-  _Float16 *Bp = pk<_Float16>(workspace, d, T, N, pl.wt);
-  int *eB = pk<int>(workspace, d, T, N, pl.ewt);
-  unsigned *cm = pk<unsigned>(workspace, d, T, N, pl.cmw);
+  _Float16 *Bp = ws.at<_Float16>(ws.lay.wt);
+  int *eB = ws.at<int>(ws.lay.ewt);
+  unsigned *cm = ws.at<unsigned>(ws.lay.cmw);
   ProfSpan ps(st, "x3_pack_bwd_stream");
   for (int dir = 0; dir < 2; dir++) {
     if (bf) {
@@ -1157,7 +492,11 @@ void pack_dx_weights(const RnnDesc &d, int l, const float *w, void *workspace, i
   }
 }
 
-void launch_bwd_stream(const RnnDesc &d, const RecParams &p, int l, const float *w, float *dxl, void *workspace,
+// dx of stacked layer l on `ov`, streamed off the backward recurrence `p`
+// just launched (gemm_x3p_bwd_stream): W_d^T packed first (unless the forward
+// did), then one persistent launch that packs dGates rows as the recurrence
+// flags them.
+void launch_bwd_stream(const RnnDesc &d, const RecParams &p, int l, const float *w, float *dxl, const RnnWs &ws,
                        int T, int N, hipStream_t ov, hipEvent_t fork, unsigned *err, const RnnPrepack *pre) {
   KCTC_HIP_CHECK(hipStreamWaitEvent(ov, fork, 0));  // after the flag reset, not after the recurrence
   // not before every workgroup of the recurrence is resident: its blocks
@@ -1167,30 +506,22 @@ void launch_bwd_stream(const RnnDesc &d, const RecParams &p, int l, const float 
   // the GEMM starts together with the recurrence)
   beside_recurrence(ov);
   const bool bf = d.prec == kPrecBf16;
-  const int NW = d.nw(), H = d.H, G4 = NW * H, KB = G4 / (bf ? 64 : 32), Din = d.din(l);
+  const int G4 = d.nw() * d.H, KB = G4 / (bf ? 64 : 32), Din = d.din(l);
   const long TN = (long)T * N;
-  const PackLay pl = pack_layout(d, T, N);
-  _Float16 *Ap = pk<_Float16>(workspace, d, T, N, pl.a), *Bp = pk<_Float16>(workspace, d, T, N, pl.wt);
-  int *eA = pk<int>(workspace, d, T, N, pl.ea), *eB = pk<int>(workspace, d, T, N, pl.ewt);
   // packed by the forward on its side stream (RnnPrepack), else here
   if (pre && pre->done) KCTC_HIP_CHECK(hipStreamWaitEvent(ov, pre->ev, 0));
-  else pack_dx_weights(d, l, w, workspace, T, N, ov);
+  else pack_dx_weights(d, l, w, ws, ov);
   X3PBwdStream a;
   a.bf16 = bf;
   a.M = (int)TN; a.N = Din; a.KB = KB;
   a.E = p.DX; a.lde = 2L * G4; a.edoff = G4;
-  a.Ap = Ap; a.eA = eA;
-  a.B = Bp; a.eB = bf ? nullptr : eB; a.sB = (long)Din * KB * 64; a.seB = Din;
+  a.Ap = ws.at<_Float16>(ws.lay.a); a.eA = ws.at<int>(ws.lay.ea);
+  a.B = ws.at<_Float16>(ws.lay.wt); a.eB = bf ? nullptr : ws.at<int>(ws.lay.ewt);
+  a.sB = (long)Din * KB * 64; a.seB = Din;
   a.C = dxl; a.ldc = Din;
-  a.part = pk<float>(workspace, d, T, N, pl.part);
-  a.part2 = pk<float>(workspace, d, T, N, pl.part2);
-  a.cnt = pk<int>(workspace, d, T, N, pl.cnt);
-  // XCD-pinned recurrence: its epochs' sc1 copies (the L2 flags are not
-  // visible here), and no block on the recurrence's XCDs
-  a.flags = p.flags + 1024 + (p.xpd ? 256 * kFlagStride : 0);  // pinned: agg_flag6 lines
-  a.nwg = p.xpd ? 1 : p.nwg; a.T = T; a.Nf = N; a.err = err; a.rg = p.rg;
-  const int pinned = whole_pinned_xcds(p);
-  if (pinned) { a.xcd_word = p.flags + kXcdWord; a.xcd_count = pinned; }
+  a.part = ws.at<float>(ws.lay.part);
+  a.part2 = ws.at<float>(ws.lay.part2);
+  a.cnt = ws.at<int>(ws.lay.cnt);
   // 128 measured best at configs[1] since the self-tagged recurrences (96
   // before: 655.7k -> 670.7k frames/s); never more than the CU budget leaves
   // beside the recurrence and the exchange's kernels (rnn.h).  Blocks landing
@@ -1198,45 +529,248 @@ void launch_bwd_stream(const RnnDesc &d, const RecParams &p, int l, const float 
   // 256-tile launch: 48 blocks keep up with the recurrence and leave the
   // other CUs beside it to the weight GEMMs (rnn_backward_weights beside)
   const bool t256 = x3p_bwd_stream_256(a.M, a.N, a.KB, bf);
-  const int nb = std::min(t256 ? 64 : 128,
-                          stream_block_budget(d.dirs * p.nwg * p.rg, true));
-  a.blocks = pinned ? nb * 8 / (8 - pinned) : nb;
+  // XCD-pinned recurrence: its epochs' sc1 copies (the L2 flags are not
+  // visible here), and no block on the recurrence's XCDs
+  const StreamProducer sp =
+      stream_producer(p, std::min(t256 ? 64 : 128, stream_block_budget(d.dirs * p.nwg * p.rg, true)));
+  a.flags = sp.lines; a.nwg = sp.nwg; a.T = T; a.Nf = N; a.err = err; a.rg = p.rg;
+  a.xcd_word = sp.xcd_word; a.xcd_count = sp.xcd_count;
+  a.blocks = sp.blocks;
   ProfSpan ps(ov, "bwd_data_stream");
   gemm_x3p_bwd_stream(ov, a);
 }
+
+// ---------------------------------------------------------------------------
+// host: forward training
+// ---------------------------------------------------------------------------
+// G = in W^T + bW (+ bR) of one stacked layer, both directions, on s: packed
+// bf16, packed split-fp16, or (a contraction too short to pack) fp32
+void project_input(const RnnDesc &d, const RnnWs &ws, hipStream_t s, long TN, int l, const float *in,
+                   const void *in_rows, const float *wl, const LayerW &lw, float *G) {
+  const int NW = d.nw(), H = d.H, dirs = d.dirs, Din = d.din(l);
+  const long ldc = (long)dirs * NW * H;
+  const float *bias = wl + lw.bW, *bias2 = (d.mode == kGru) ? nullptr : wl + lw.bR;
+  if (d.prec == kPrecBf16 && use_x3(Din, 32)) {
+    // bf16 gate GEMM: input rows and W rows packed as bf16, fp32 accumulation
+    // the input rows come packed from the previous component's forward (in_rows)
+    const bool rows_in = l == 0 && in_rows && Din % 64 == 0;
+    __bf16 *Ap = rows_in ? static_cast<__bf16 *>(const_cast<void *>(in_rows)) : ws.at<__bf16>(ws.lay.a);
+    __bf16 *Bp = ws.at<__bf16>(ws.lay.b);
+    const int KB = (Din + 63) / 64;
+    {
+      ProfSpan ps(s, "x3_pack");
+      if (!rows_in) bf16_pack_rows(s, in, Din, (int)TN, Din, Ap);
+      bf16_pack_rows(s, wl, Din, NW * H, Din, Bp, dirs, lw.pls, (long)NW * H * KB * 64);
+    }
+    X3PArgs x;
+    x.bf16 = true;
+    x.M = (int)TN; x.N = NW * H; x.KB = KB;
+    x.A = reinterpret_cast<const _Float16 *>(Ap); x.B = reinterpret_cast<const _Float16 *>(Bp);
+    x.C = G; x.ldc = ldc; x.bias = bias; x.bias2 = bias2;
+    x.batch = dirs; x.sA = 0; x.sB = (long)NW * H * KB * 64;
+    x.sC = (long)NW * H; x.sBias = lw.pls;
+    ProfSpan ps(s, "gemm_fwd_proj");
+    gemm_x3p(s, x);
+  } else if (use_x3(Din, 32)) {
+    // input rows (a lower stacked layer's output is bounded; the component
+    // input and RELU outputs get per-row exponents) and W rows, packed
+    _Float16 *Ap = ws.at<_Float16>(ws.lay.a), *Bp = ws.at<_Float16>(ws.lay.b);
+    int *eA = ws.at<int>(ws.lay.ea), *eB = ws.at<int>(ws.lay.eb);
+    const int KB = (Din + 31) / 32;
+    {
+      ProfSpan ps(s, "x3_pack");
+      x3p_pack_rows(s, in, Din, (int)TN, Din, Ap, eA, (l > 0 && bounded_out(d)) ? 1.f : 0.f);
+      x3p_pack_rows(s, wl, Din, NW * H, Din, Bp, eB, 0.f, dirs, lw.pls, (long)NW * H * KB * 64, (long)NW * H);
+    }
+    X3PArgs x;
+    x.M = (int)TN; x.N = NW * H; x.KB = KB;
+    x.A = Ap; x.B = Bp; x.eA = eA; x.eB = eB;
+    x.C = G; x.ldc = ldc; x.bias = bias; x.bias2 = bias2;
+    x.batch = dirs; x.sA = 0; x.seA = 0; x.sB = (long)NW * H * KB * 64; x.seB = (long)NW * H;
+    x.sC = (long)NW * H; x.sBias = lw.pls;
+    ProfSpan ps(s, "gemm_fwd_proj");
+    gemm_x3p(s, x);
+  } else {
+    GemmArgs g;
+    g.transA = false; g.transB = true;
+    g.M = (int)TN; g.N = NW * H; g.K = Din;
+    g.A = in; g.lda = Din;
+    g.B = wl; g.ldb = Din;
+    g.C = G; g.ldc = ldc;
+    g.bias = bias; g.bias2 = bias2;
+    g.batch = dirs; g.strideA = 0; g.strideB = lw.pls; g.strideC = (long)NW * H; g.strideBias = lw.pls;
+    ProfSpan ps(s, "gemm_fwd_proj");
+    gemm_f32(s, g);
+  }
+}
+
+// The forward's share of RecParams, and the fills its hand-off needs, on s
+void fwd_rec_params(RecParams &p, const RnnDesc &d, const RecPlan &pl, const RnnWs &ws, float *R0,
+                    const RnnReserveLayout &lay, bool chained, bool rowchain, hipStream_t s) {
+  const long TN = (long)p.T * p.N;
+  p.ncol = (d.nw() * pl.U + 15) / 16 * 16;
+  p.sync = pl.ver == 4 ? kSyncFlag : kSyncData;
+  p.allow_local = 0;
+  p.xch = ws.xch();
+  p.poll_sleep = 1;
+  p.gla = 3;  // G rows fetched 3 steps ahead (IO waves)
+  if (pl.ver != 6) return;
+  if (bf16_io(d)) {  // the output also as packed bf16 rows and columns
+    p.yr = reinterpret_cast<__bf16 *>(R0 + lay.pkyr);
+    p.yc = reinterpret_cast<__bf16 *>(R0 + lay.pkyc);
+    p.kbt64 = lay.kbt64;
+    if (lay.kbt64 > TN)
+      KCTC_HIP_CHECK(hipMemset2DAsync(p.yc + TN, sizeof(__bf16) * lay.kbt64, 0, sizeof(__bf16) * (lay.kbt64 - TN),
+                                      (size_t)d.dirs * d.H, s));
+  }
+  // XCD-pinned: a streamed projection gets sc1 copies of the step images and flags
+  p.fcopy = p.xpd && chained;
+  p.ysc1 = rowchain ? 1 : 0;
+  p.allow_local = p.xpd ? 1 : 0;
+  // self-tagged hand-off (the kernel takes it for split-fp16 variants other
+  // than kRec6IoWave, without a write-through copy): the ring starts at tag 1
+  p.dtag = d.prec != kPrecBf16 && p.ring == 2 && !p.fcopy && p.T >= 2;
+  if (p.dtag) {  // rnn_fwd_rec6's ring: after T step images of XS = 64 H rg halves (2 dirs, hi / lo, 16 rows)
+    const size_t xs = sizeof(_Float16) * 64 * (size_t)d.H * p.rg;
+    KCTC_HIP_CHECK(hipMemsetAsync(reinterpret_cast<char *>(p.xch) + xs * p.T, 0x01, 2 * xs, s));
+  }
+}
+
+// x^T of the weight GEMMs beside the forward recurrence, off its XCDs
+// (rnn_backward_weights' packs; RnnPrepack::wgrad)
+void prepack_x_cols(const RnnDesc &d, const RnnWs &ws, const float *in, long TN, const RnnPrepack &pre) {
+  hipStream_t ss = pre.stream;
+  const int Din = d.din(0);
+  int *pc = ws.at<int>(ws.lay.pcnt);  // item counters
+  KCTC_HIP_CHECK(hipMemsetAsync(pc, 0, sizeof(int) * 3, ss));
+  const unsigned *av = rnn_pinned_xcds();
+  const int nx = std::max(1, rnn_usable_cus() / kCusPerXcd);
+  ProfSpan ps(ss, "x3_pack_w_fwd");
+  x3p_pack_cols(ss, in, Din, (int)TN, Din, 0, ws.at<_Float16>(ws.lay.xt), ws.at<int>(ws.lay.ext), nullptr,
+                pre.in_bound, 1, 0, 0, 0, 0, av, nx, pc);
+}
+// ... and y^T after it (and after the joins: s does not wait for it)
+void prepack_y_cols(const RnnDesc &d, const RnnWs &ws, const float *out, long TN, int N, RnnPrepack &pre,
+                    hipStream_t s) {
+  hipStream_t ss = pre.stream;
+  KCTC_HIP_CHECK(hipStreamWaitEvent(ss, fork_event(s), 0));
+  const int H = d.H, dirs = d.dirs;
+  const long KBt = (TN + 31) / 32;
+  int *pc = ws.at<int>(ws.lay.pcnt);
+  const unsigned *av = rnn_pinned_xcds();
+  const int nx = std::max(1, rnn_usable_cus() / kCusPerXcd);
+  const long ldy = (long)dirs * H;
+  {
+    ProfSpan ps(ss, "x3_pack_w_fwd");
+    for (int dir = 0; dir < dirs; dir++)
+      x3p_pack_cols(ss, out + (long)dir * H, ldy, (int)TN, H, dir == 0 ? N : -N,
+                    ws.at<_Float16>(ws.lay.yt) + (long)dir * H * KBt * 64, ws.at<int>(ws.lay.eyt) + dir * H,
+                    nullptr, 1.f, 1, 0, 0, 0, 0, av, nx, pc + 1 + dir);
+  }
+  KCTC_HIP_CHECK(hipEventRecord(pre.wev, ss));
+  pre.wdone = true;
+}
+
 }  // namespace
+
+thread_local bool g_last_bwd_scratch_free = true;
+bool rnn_last_bwd_scratch_free() { return g_last_bwd_scratch_free; }
+
+bool rnn_packed_output(const RnnDesc &d, int T, int N, void *reserve, const void **rows, const void **cols) {
+  *rows = *cols = nullptr;
+  if (!bf16_io(d) || !reserve) return false;
+  const RnnReserveLayout lay = rnn_reserve_layout(d, T, N);
+  float *res = static_cast<float *>(reserve);
+  *rows = res + lay.pkyr;
+  *cols = res + lay.pkyc;
+  return true;
+}
+
+int rnn_forward_training(const RnnDesc &d, hipStream_t s, int T, int N, const float *x,
+                         const float *w, float *y, void *workspace, size_t ws_bytes,
+                         void *reserve, size_t res_bytes, unsigned *err, RnnFwdChain *chain,
+                         bool input_projected, const void *in_rows, RnnPrepack *pre) {
+  RecScope rec_scope;  // the side launches' residency gates (beside_recurrence)
+  if (chain) chain->done = false;
+  if (pre) pre->done = pre->wdone = false;
+  if (T <= 0 || N <= 0 || N > 16 * kMaxRT || d.H % 16) return KRNN_NOT_SUPPORTED;
+  const RnnReserveLayout lay = rnn_reserve_layout(d, T, N);
+  if (res_bytes < sizeof(float) * (size_t)lay.total) return KRNN_BAD_PARAM;
+  const RnnWs ws(d, T, N, workspace);
+  if (ws_bytes < ws.bytes()) return KRNN_BAD_PARAM;
+  const RecPlan pl = plan_rec(d, N, true);
+  if (!pl) return KRNN_NOT_SUPPORTED;
+  const bool v6 = pl.ver == 6;
+  const int H = d.H, dirs = d.dirs;
+  const long TN = (long)T * N;
+  float *res = static_cast<float *>(reserve);
+  const float *in = x;
+  for (int l = 0; l < d.layers; l++) {
+    const bool last = l == d.layers - 1;
+    float *R0 = res + lay.per_layer * l;
+    float *out = last ? y : R0 + lay.out;
+    const LayerW lw = layer_w(d, l);
+    const float *wl = w + lw.pl0;
+    if (pl.ver == 3) KCTC_HIP_CHECK(hipMemsetAsync(out, 0xFF, sizeof(float) * TN * dirs * H, s));
+    // (layer 0 may come projected: streamed by the previous component)
+    if (!(l == 0 && input_projected)) project_input(d, ws, s, TN, l, in, in_rows, wl, lw, R0 + lay.G);
+    RecParams p = rec_params(d, pl, ws, T, N, wl, lw, R0, lay, out, err, s);
+    // what runs beside this recurrence: the next component's projection off
+    // its step images or its y rows, and (one-layer descriptors) the packs
+    // the backward would otherwise wait for -- W^T of its streamed dx GEMM
+    // (rnn_backward_data's `streamed` shapes), x^T / y^T of its weight GEMMs
+    const bool chained = last && chain_ok(pl, d, T, N, chain);
+    const bool rowchain = !chained && last && chain_rows_ok(pl, d, T, N, chain);
+    fwd_rec_params(p, d, pl, ws, R0, lay, chained, rowchain, s);
+    const bool prepack = pre && pre->dx && pre->stream && pre->ev && v6 && d.layers == 1 &&
+                         bwd_dx_stream_ok(plan_rec(d, N, false), d, 0, T, N);
+    const bool prepack_w = pre && pre->stream && pre->wev && pre->wgrad && pre->in_bound > 0.f && v6 &&
+                           d.layers == 1 && d.prec != kPrecBf16 && T > 1 && bounded_out(d) && use_x3((int)TN) &&
+                           pl.scratch_free;
+    const hipEvent_t fork = (chained || prepack || prepack_w || rowchain) ? fork_event(s) : nullptr;
+    RecTrace tr;
+    launch_planned(d, pl, true, p, tr, rec_scope, s);
+    if (prepack) {  // beside the recurrence, once it is resident
+      KCTC_HIP_CHECK(hipStreamWaitEvent(pre->stream, fork, 0));
+      beside_recurrence(pre->stream);
+      pack_dx_weights(d, 0, w, ws, pre->stream);
+      KCTC_HIP_CHECK(hipEventRecord(pre->ev, pre->stream));
+      pre->done = true;
+    }
+    if (prepack_w) {
+      if (!prepack) KCTC_HIP_CHECK(hipStreamWaitEvent(pre->stream, fork, 0));
+      beside_recurrence(pre->stream);
+      prepack_x_cols(d, ws, in, TN, *pre);
+    }
+    if (chained) {
+      launch_chain_proj(d, p, fork, T, N, *chain, err);
+      join_stream(s, chain->side);
+    }
+    if (rowchain) {
+      launch_chain_rows(d, p, fork, T, N, *chain, err);
+      join_stream(s, chain->side);
+    }
+    if (prepack_w) prepack_y_cols(d, ws, out, TN, N, *pre, s);
+    tr.dump("fwd", s, pl.grid, p.nwg, T, dirs, pl.ver, p.xpd);
+    in = out;
+  }
+  return KRNN_OK;
+}
 
 // ---------------------------------------------------------------------------
 // streamed weight gradients of the bottom component (rnn.h RnnWgradStream)
 // ---------------------------------------------------------------------------
 namespace {
-// One wave: returns once every v6 flag line (stride kFlagStride words) holds
-// >= epoch, the recurrence reported an error, or after 3 s (then err bit 3).
-// Every exit decision is wave-uniform; the error store follows the loop.
-__global__ __launch_bounds__(64) void rec_gate_kernel(const unsigned *flags, int nlines, unsigned epoch,
-                                                      unsigned *err) {
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  int spins = 0;
-  bool late = false;
-  while (true) {
-    bool ok = true;
-    for (int i = threadIdx.x; i < nlines; i += 64)
-      ok &= __hip_atomic_load(flags + (long)i * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= epoch;
-    if (__all(ok)) break;
-    if ((++spins & 255) == 0) {
-      const unsigned e = __builtin_amdgcn_readfirstlane(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      if (e) break;
-      late = __builtin_amdgcn_s_memrealtime() - t0 > 300000000ull;
-      if (late) break;
-    }
-    __builtin_amdgcn_s_sleep(16);
-  }
-  if (late && threadIdx.x == 0) atomicOr(err, 8u);
+// the dynamic tile counter of a weight GEMM (flag word kTileWordW / kTileWordR
+// of the workspace: the recurrences of this layer, which use the flag area,
+// are done); none without a persistent grid
+int *tile_counter(const RnnWs &ws, int word, int max_blocks) {
+  return max_blocks > 0 ? reinterpret_cast<int *>(ws.flags() + word) : nullptr;
 }
 
 // dW_dir += DX_dir^T x and dR_dir += DX_dir^T h_prev over the frames [ta, tb)
 // of direction dir (layer 0 of a one-layer component, split-fp16, LSTM: E == DX)
-void wgrad_frames(const RnnDesc &d, hipStream_t s, int T, int N, const float *x, const float *y, void *workspace,
+void wgrad_frames(const RnnDesc &d, hipStream_t s, int T, int N, const float *x, const float *y, const RnnWs &ws,
                   float *dw, void *reserve, int max_blocks, float in_bound, int dir, int ta, int tb) {
   if (tb <= ta) return;
   const RnnReserveLayout lay = rnn_reserve_layout(d, T, N);
@@ -1244,15 +778,9 @@ void wgrad_frames(const RnnDesc &d, hipStream_t s, int T, int N, const float *x,
   const long ldg = (long)dirs * G4, ldy = (long)dirs * H;
   const int R = (tb - ta) * N, KB = (R + 31) / 32;
   const float *DX = static_cast<const float *>(reserve) + lay.E;
-  const PackLay pl = pack_layout(d, T, N);
-  _Float16 *DXt = pk<_Float16>(workspace, d, T, N, pl.a), *Xt = pk<_Float16>(workspace, d, T, N, pl.b);
-  _Float16 *Yt = pk<_Float16>(workspace, d, T, N, pl.c);
-  int *eDX = pk<int>(workspace, d, T, N, pl.ea), *eX = pk<int>(workspace, d, T, N, pl.eb);
-  int *eY = pk<int>(workspace, d, T, N, pl.ec);
-  unsigned *cm = pk<unsigned>(workspace, d, T, N, pl.cm);
-  unsigned *fl = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + flags_offset(d, T, N));
-  float *ws = static_cast<float *>(workspace);
-  const long ws_floats = drec_split_floats(d, T, N);
+  _Float16 *DXt = ws.at<_Float16>(ws.lay.a), *Xt = ws.at<_Float16>(ws.lay.b), *Yt = ws.at<_Float16>(ws.lay.c);
+  int *eDX = ws.at<int>(ws.lay.ea), *eX = ws.at<int>(ws.lay.eb), *eY = ws.at<int>(ws.lay.ec);
+  unsigned *cm = ws.at<unsigned>(ws.lay.cm);
   {
     ProfSpan ps(s, "x3_pack_w");
     const float *src = DX + (long)ta * N * ldg + (long)dir * G4;
@@ -1272,73 +800,209 @@ void wgrad_frames(const RnnDesc &d, hipStream_t s, int T, int N, const float *x,
       else x3p_pack_cols(s, yd + (long)(ta + 1) * N * ldy, ldy, R, H, 0, Yt, eY, nullptr, 1.f);
     }
   }
-  auto split_for = [&](int n) {
-    int sp = x3p_pick_split(G4, n, KB, 1);
-    while (sp > 1 && (long)sp * G4 * n > ws_floats) sp--;
-    return sp;
+  auto gemm = [&](int n, const _Float16 *B, const int *eB, float *C, int word, const char *name) {
+    X3PArgs a;
+    a.M = G4; a.N = n; a.KB = KB;
+    a.A = DXt; a.eA = eDX; a.B = B; a.eB = eB;
+    a.C = C; a.ldc = n; a.beta = 1.f; a.batch = 1;
+    a.split_k = x3p_pick_split(G4, n, KB, 1);
+    while (a.split_k > 1 && (long)a.split_k * G4 * n > ws.split_floats) a.split_k--;
+    a.ws = ws.split_slab();
+    a.max_blocks = max_blocks;
+    a.tile_counter = tile_counter(ws, word, max_blocks);
+    ProfSpan ps(s, name);
+    gemm_x3p(s, a);
   };
-  const long pl0 = d.lin_offset(dir, 0, false);
-  {
-    X3PArgs a;
-    a.M = G4; a.N = Din; a.KB = KB;
-    a.A = DXt; a.eA = eDX; a.B = Xt; a.eB = eX;
-    a.C = dw + pl0; a.ldc = Din; a.beta = 1.f; a.batch = 1;
-    a.split_k = split_for(Din); a.ws = ws;
-    a.max_blocks = max_blocks;
-    if (max_blocks > 0) a.tile_counter = reinterpret_cast<int *>(fl + 1008);
-    ProfSpan ps(s, "gemm_bwd_w");
-    gemm_x3p(s, a);
-  }
-  {
-    X3PArgs a;
-    a.M = G4; a.N = H; a.KB = KB;
-    a.A = DXt; a.eA = eDX; a.B = Yt; a.eB = eY;
-    a.C = dw + d.lin_offset(dir, NW, false); a.ldc = H; a.beta = 1.f; a.batch = 1;
-    a.split_k = split_for(H); a.ws = ws;
-    a.max_blocks = max_blocks;
-    if (max_blocks > 0) a.tile_counter = reinterpret_cast<int *>(fl + 1009);
-    ProfSpan ps(s, "gemm_bwd_r");
-    gemm_x3p(s, a);
-  }
+  gemm(Din, Xt, eX, dw + d.lin_offset(dir, 0, false), kTileWordW, "gemm_bwd_w");
+  gemm(H, Yt, eY, dw + d.lin_offset(dir, NW, false), kTileWordR, "gemm_bwd_r");
 }
 
-// dbW += sum dGx, dbR += sum dGh of layer l from the recurrence's per-group partials
-void wgrad_bias(const RnnDesc &d, hipStream_t s, int T, int N, float *dw, void *reserve, int l) {
+// dbW += sum dGx, dbR += sum dGh of layer l from the partials of its backward recurrence `pl`
+void wgrad_bias(const RecPlan &pl, const RnnDesc &d, hipStream_t s, int T, int N, float *dw, void *reserve, int l) {
   const RnnReserveLayout lay = rnn_reserve_layout(d, T, N);
-  const int NW = d.nw(), H = d.H, dirs = d.dirs, G4 = NW * H;
+  const int dirs = d.dirs, G4 = d.nw() * d.H;
   const float *R0 = static_cast<const float *>(reserve) + lay.per_layer * l;
-  const long pl0 = d.lin_offset(l * dirs, 0, false), pls = d.pl_size(l);
-  float *dwl = dw + pl0;
-  const long bW = d.lin_offset(l * dirs, 0, true) - pl0;
-  const long bR = d.lin_offset(l * dirs, NW, true) - pl0;
+  const LayerW lw = layer_w(d, l);
+  float *dwl = dw + lw.pl0;
   // (v6: one partial per row group, [group][dir][2][G], added in group order)
-  const V6Cfg c6b = pick6(d, N, false);
-  const int rg = c6b ? c6b.rg : 1;
+  const int rg = pl.ver == 6 ? pl.rg : 1;
   for (int gi = 0; gi < rg; gi++)
     for (int dir = 0; dir < dirs; dir++) {
       const float *part = R0 + lay.bias + ((long)gi * dirs + dir) * 2 * G4;
-      clip_sgd_update(s, dwl + dir * pls + bW, part, G4, 1.f, 0.f);
-      clip_sgd_update(s, dwl + dir * pls + bR, part + G4, G4, 1.f, 0.f);
+      clip_sgd_update(s, dwl + dir * lw.pls + lw.bW, part, G4, 1.f, 0.f);
+      clip_sgd_update(s, dwl + dir * lw.pls + lw.bR, part + G4, G4, 1.f, 0.f);
     }
 }
-}  // namespace
 
+bool wgrad_stream_ok(const RecPlan &pl, const RnnDesc &d, int T, int N) {
+  if (pl.ver != 6 || !use_x3((int)((long)T * N)) || !use_x3(d.nw() * d.H) || !pl.scratch_free) return false;
+  return (long)T * N * d.din(0) * 4 < (1L << 31);
+}
 // Off by default (KCTC_WGRAD_STREAM=1 turns it on): measured on configs[1]
 // 470.4k -> 467.0k (2 chunks), 466.1k (4), 454.5k (8) frames/s: the chunk
 // GEMMs beside the backward recurrence slow it (33.0 -> 33.3-33.5 ms/step)
 // and the per-chunk transposes add packing, more than the 1 ms tail saved.
+bool wgrad_stream_shape(const RnnDesc &d, int T, int N) {
+  return env_int("KCTC_WGRAD_STREAM", 0) && d.layers == 1 && d.dirs == 2 && d.mode == kLstm && d.prec == kPrecX3 &&
+         T >= 8 && N <= 16;
+}
+
+// The weight gradients of the bottom component on wgrad.side, chunk by chunk
+// as the unpinned backward recurrence `p` just launched on s finishes frames
+void launch_wgrad_stream(const RecPlan &pl, const RnnDesc &d, const RecParams &p, hipEvent_t fork, int T, int N,
+                         const float *y, const RnnWs &ws, void *reserve, unsigned *err, RnnWgradStream &wgrad,
+                         hipStream_t s) {
+  // chunk c of C: direction 0 frames [T - b(c+1), T - b(c)), direction 1
+  // [b(c), b(c+1)), b(c) = c T / C; complete once every flag line holds
+  // epoch b(c+1) + 2 (rows of step k are out at epoch k + 3)
+  hipStream_t ws2 = wgrad.side;
+  KCTC_HIP_CHECK(hipStreamWaitEvent(ws2, fork, 0));  // after the flag reset
+  beside_recurrence(ws2);
+  const int C = std::max(1, std::min(wgrad.chunks, T / 4));
+  const unsigned *lines = epoch_lines(p);  // (not pinned: the workgroups' own lines)
+  const int nlines = p.rg * p.dirs * p.nwg;
+  for (int c = 0; c < C; c++) {
+    const int b0 = (int)((long)c * T / C), b1 = (int)((long)(c + 1) * T / C);
+    rec_epoch_gate(ws2, lines, nlines, (unsigned)(b1 + 2), err);
+    wgrad_frames(d, ws2, T, N, wgrad.x, y, ws, wgrad.dw, reserve, wgrad.max_blocks, wgrad.in_bound, 0, T - b1,
+                 T - b0);
+    wgrad_frames(d, ws2, T, N, wgrad.x, y, ws, wgrad.dw, reserve, wgrad.max_blocks, wgrad.in_bound, 1, b0, b1);
+  }
+  join_stream(ws2, s);  // the bias partials are written after the last flag
+  wgrad_bias(pl, d, ws2, T, N, wgrad.dw, reserve, 0);
+  wgrad.done = true;
+}
+}  // namespace
+
 bool rnn_wgrad_stream_ok(const RnnDesc &d, int T, int N) {
-  if (!env_int("KCTC_WGRAD_STREAM", 0) || d.layers != 1 || d.dirs != 2 || d.mode != kLstm ||
-      d.prec != kPrecX3 || T < 8 || N > 16)
-    return false;
-  if (!pick6(d, N, false) || !use_x3((int)((long)T * N)) || !use_x3(d.nw() * d.H) || !rec6_scratch_free(d, N, false))
-    return false;
-  return (long)T * N * d.din(0) * 4 < (1L << 31);
+  return wgrad_stream_shape(d, T, N) && wgrad_stream_ok(plan_rec(d, N, false), d, T, N);
 }
 
 // ---------------------------------------------------------------------------
 // host: backward data (dGates into the reserve, dx)
 // ---------------------------------------------------------------------------
+namespace {
+// The backward's share of RecParams, and the fills its outputs need, on s
+void bwd_rec_params(RecParams &p, const RnnDesc &d, const RecPlan &pl, const RnnWs &ws, float *R0,
+                    const RnnReserveLayout &lay, const float *dy, float *E, float *DX, bool e_sc1, hipStream_t s) {
+  const int NW = d.nw(), H = d.H, dirs = d.dirs, T = p.T, N = p.N;
+  const long TN = (long)T * N;
+  p.ncol = 16;
+  p.dy = dy; p.E = E; p.DX = DX; p.bias = R0 + lay.bias;
+  p.sync = kSyncFlag;
+  p.allow_local = 0;
+  if (pl.ver != 6) {
+    p.xch = ws.xch();
+    return;
+  }
+  // XCD-pinned: the partial-dh hand-off in the XCD's L2 (configs[1]: 3.36 ->
+  // 2.70 us per step with the streamed dx GEMM beside it (2.41 without),
+  // 468k -> 511k frames/s)
+  p.allow_local = 1;
+  p.poll_sleep = 1;
+  p.bfpart = 1;
+  p.xch = xch_acquire(sizeof(float) * (size_t)T * dirs * p.nwg * (16 * H + 64) * p.rg, s);
+  // self-tagged hand-off (fp32 partials through the L2 ring): the two ring
+  // images start with tag 1 in every word (steps 0 and 1 publish tag 0)
+  p.dtag = d.prec != kPrecBf16 && p.ring == 2 && p.xpd && T >= 2;
+  if (p.dtag)
+    KCTC_HIP_CHECK(hipMemsetAsync(p.xch, 0x01, sizeof(float) * 2 * (size_t)dirs * p.nwg * (16 * H + 64) * p.rg, s));
+  p.e_sc1 = e_sc1 ? 1 : 0;  // dGates rows written through for a streaming consumer
+  // bf16: dGates straight into the packed operands of the dx / dW / dR GEMMs
+  // (no fp32 rows, no pack passes over them; KCTC_BF16_DIRECT=0: the fp32
+  // rows and the pack kernels as in round 3), beside e_sc1's write-through rows when streamed
+  if (bf16_direct(d, 6)) {
+    p.dxr = reinterpret_cast<__bf16 *>(R0 + lay.pkxr);
+    p.dxt = reinterpret_cast<__bf16 *>(R0 + lay.pkxt);
+    p.eshift = bf16_io(d) ? 1 : 0;
+    p.et = (d.mode == kGru || p.eshift) ? reinterpret_cast<__bf16 *>(R0 + lay.pket) : p.dxt;
+    p.kbt64 = lay.kbt64;
+    const size_t pitch = sizeof(__bf16) * lay.kbt64;
+    const size_t rows = (size_t)NW * H;  // per direction
+    if (lay.kbt64 > TN)  // the frame tail of every packed row stays zero
+      KCTC_HIP_CHECK(hipMemset2DAsync(p.dxt + TN, pitch, 0, sizeof(__bf16) * (lay.kbt64 - TN), dirs * rows, s));
+    if (p.eshift) {  // E^T shifted: direction 0 from TN - N on, direction 1 before N and from TN on
+      KCTC_HIP_CHECK(hipMemset2DAsync(p.et + TN - N, pitch, 0, sizeof(__bf16) * (lay.kbt64 - TN + N), rows, s));
+      KCTC_HIP_CHECK(hipMemset2DAsync(p.et + rows * lay.kbt64, pitch, 0, sizeof(__bf16) * N, rows, s));
+      if (lay.kbt64 > TN)
+        KCTC_HIP_CHECK(hipMemset2DAsync(p.et + rows * lay.kbt64 + TN, pitch, 0, sizeof(__bf16) * (lay.kbt64 - TN),
+                                        rows, s));
+    } else if (d.mode == kGru && lay.kbt64 > TN) {
+      KCTC_HIP_CHECK(hipMemset2DAsync(p.et + TN, pitch, 0, sizeof(__bf16) * (lay.kbt64 - TN), dirs * rows, s));
+    }
+  }
+  p.cmax = ws.at<unsigned>(ws.lay.cme);
+  if (p.rg > 1)  // max over the row groups by atomicMax on the float bits
+    KCTC_HIP_CHECK(hipMemsetAsync(p.cmax, 0, sizeof(unsigned) * 2 * dirs * NW * H, s));
+}
+
+// dx_l = sum_dir DX_dir W_dir on s after the recurrence (not streamed): packed
+// bf16 (dxr: the dGates rows the recurrence wrote packed, or null), packed
+// split-fp16, or (few gate columns) fp32
+void dx_gemm(const RnnDesc &d, const RnnWs &ws, hipStream_t s, long TN, int l, const float *DX, __bf16 *dxr,
+             const float *wl, long pls, float *dxl) {
+  const int dirs = d.dirs, Din = d.din(l);
+  const long G4 = (long)d.nw() * d.H;
+  if (d.prec == kPrecBf16 && use_x3((int)G4)) {
+    // dGates rows and W^T rows (columns of W) packed as bf16
+    const int KB = (int)((G4 + 63) / 64);
+    __bf16 *Ap = dxr ? dxr : ws.at<__bf16>(ws.lay.a), *Bp = ws.at<__bf16>(ws.lay.b);
+    {
+      ProfSpan ps(s, "x3_pack");
+      if (!dxr) bf16_pack_rows(s, DX, (long)dirs * G4, (int)TN, (int)G4, Ap, dirs, G4, TN * KB * 64);
+      for (int dir = 0; dir < dirs; dir++)
+        bf16_pack_cols(s, wl + dir * pls, Din, (int)G4, Din, 0, Bp + (long)dir * Din * KB * 64);
+    }
+    for (int dir = 0; dir < dirs; dir++) {
+      ProfSpan ps(s, "gemm_bwd_data");
+      X3PArgs x;
+      x.bf16 = true;
+      x.M = (int)TN; x.N = Din; x.KB = KB;
+      x.A = reinterpret_cast<const _Float16 *>(Ap + (long)dir * TN * KB * 64);
+      x.B = reinterpret_cast<const _Float16 *>(Bp + (long)dir * Din * KB * 64);
+      x.C = dxl; x.ldc = Din; x.beta = dir == 0 ? 0.f : 1.f;
+      gemm_x3p(s, x);
+    }
+  } else if (use_x3((int)G4)) {
+    const int KB = (int)((G4 + 31) / 32);
+    _Float16 *Ap = ws.at<_Float16>(ws.lay.a), *Bp = ws.at<_Float16>(ws.lay.b);
+    int *eA = ws.at<int>(ws.lay.ea), *eB = ws.at<int>(ws.lay.eb);
+    unsigned *cm = ws.at<unsigned>(ws.lay.cm);
+    {
+      // dGates rows (frames, per direction) and W^T rows (input dims), packed over the gates
+      ProfSpan ps(s, "x3_pack");
+      x3p_pack_rows(s, DX, (long)dirs * G4, (int)TN, (int)G4, Ap, eA, 0.f, dirs, G4, TN * KB * 64, TN);
+      for (int dir = 0; dir < dirs; dir++) {
+        absmax_f32(s, wl + dir * pls, Din, (int)G4, Din, nullptr, cm);
+        x3p_pack_cols(s, wl + dir * pls, Din, (int)G4, Din, 0, Bp + (long)dir * Din * KB * 64, eB + dir * Din, cm,
+                      0.f);
+      }
+    }
+    for (int dir = 0; dir < dirs; dir++) {
+      ProfSpan ps(s, "gemm_bwd_data");
+      X3PArgs x;
+      x.M = (int)TN; x.N = Din; x.KB = KB;
+      x.A = Ap + (long)dir * TN * KB * 64; x.eA = eA + (long)dir * TN;
+      x.B = Bp + (long)dir * Din * KB * 64; x.eB = eB + dir * Din;
+      x.C = dxl; x.ldc = Din; x.beta = dir == 0 ? 0.f : 1.f;
+      gemm_x3p(s, x);
+    }
+  } else {
+    for (int dir = 0; dir < dirs; dir++) {
+      ProfSpan ps(s, "gemm_bwd_data");
+      GemmArgs g;
+      g.transA = false; g.transB = false;
+      g.M = (int)TN; g.N = Din; g.K = (int)G4;
+      g.A = DX + (long)dir * G4; g.lda = (long)dirs * G4;
+      g.B = wl + dir * pls; g.ldb = Din;
+      g.C = dxl; g.ldc = Din;
+      g.beta = dir == 0 ? 0.f : 1.f;
+      gemm_f32(s, g);
+    }
+  }
+}
+}  // namespace
+
 int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float *y,
                       const float *dy, const float *w, float *dx, void *workspace,
                       size_t ws_bytes, void *reserve, size_t res_bytes, unsigned *err,
@@ -1348,13 +1012,11 @@ int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float
   if (T <= 0 || N <= 0 || N > 16 * kMaxRT || d.H % 16) return KRNN_NOT_SUPPORTED;
   const RnnReserveLayout lay = rnn_reserve_layout(d, T, N);
   if (res_bytes < sizeof(float) * (size_t)lay.total) return KRNN_BAD_PARAM;
-  const V6Cfg c6 = pick6(d, N, false);
-  const int U6 = c6.U;
-  const int U4 = U6 ? 0 : pick_bwd_u4(d, N);
-  const int ver = U6 ? 6 : U4 ? 4 : 3;
-  const int U = U6 ? U6 : U4 ? U4 : pick_bwd_u(d, N);
-  if (d.prec == kPrecBf16 && ver != 6) return KRNN_NOT_SUPPORTED;
-  if (!U) return KRNN_NOT_SUPPORTED;
+  const RecPlan pl = plan_rec(d, N, false);
+  if (!pl) return KRNN_NOT_SUPPORTED;
+  const RnnWs ws(d, T, N, workspace);
+  if (ws_bytes < ws.bytes()) return KRNN_BAD_PARAM;
+  const bool v6 = pl.ver == 6;
   const int NW = d.nw(), H = d.H, dirs = d.dirs;
   const long TN = (long)T * N;
   float *res = static_cast<float *>(reserve);
@@ -1362,197 +1024,37 @@ int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float
   for (int l = d.layers - 1; l >= 0; l--) {
     float *R0 = res + lay.per_layer * l;
     const float *out = (l == d.layers - 1) ? y : R0 + lay.out;
-    const int Din = d.din(l);
-    const long pl0 = d.lin_offset(l * dirs, 0, false);
-    const float *wl = w + pl0;
-    const long pls = d.pl_size(l);
+    const LayerW lw = layer_w(d, l);
+    const float *wl = w + lw.pl0;
     float *E = R0 + lay.E;
     float *DX = d.mode == kGru ? R0 + lay.DX : E;
-    if (ver == 3) KCTC_HIP_CHECK(hipMemsetAsync(E, 0xFF, sizeof(float) * TN * dirs * NW * H, s));
-    RecParams p{};
-    p.T = T; p.N = N; p.H = H; p.dirs = dirs; p.U = U; p.nwg = H / U;
-    p.ncol = 16; p.Npad = (N + 15) / 16 * 16;
-    p.w = wl; p.pl_stride = pls; p.r_off = d.lin_offset(l * dirs, NW, false) - pl0;
-    p.bR_off = d.lin_offset(l * dirs, NW, true) - pl0;
-    p.G = R0 + lay.G; p.y = const_cast<float *>(out); p.aux = R0 + lay.aux;
-    p.dy = dcur; p.E = E; p.DX = DX; p.bias = R0 + lay.bias; p.err = err;
-    p.sync = kSyncFlag;
-    p.allow_local = 0;
-    if (ws_bytes < rnn_workspace_bytes(d, T, N)) return KRNN_BAD_PARAM;
-    p.flags = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + flags_offset(d, T, N));
-    KCTC_HIP_CHECK(hipMemsetAsync(p.flags, 0, kFlagBytes, s));
-    const size_t lds = ver == 6 ? bwd6_lds_bytes(d, c6) : bwd_lds_bytes(d, N, U, ver);
-    p.xpd = ver == 4 ? v4_xpd(d, U) : 1;
-    p.rg = ver == 6 ? c6.rg : 1;
-    p.gs = ver == 6 ? c6.gs : 16;
-    if (ver == 6) {
-      // XCD-pinned backward (xcd_mask): each (row group, direction) on one
-      // XCD, the partial-dh hand-off in that XCD's L2, through a ring of two
-      // step images (L2-resident).  configs[1]: 3.36 -> 2.70 us per step with
-      // the streamed dx GEMM beside it (2.41 without), 468k -> 511k frames/s
-      p.xpd = xcd_mask(d, N, false) ? 1 : 0;
-      p.ring = p.xpd ? 2 : 0;
-      p.allow_local = 1;
-      p.poll_sleep = 1;
-      p.bfpart = 1;
-      p.xch = xch_acquire(sizeof(float) * (size_t)T * dirs * p.nwg * (16 * H + 64) * p.rg, s);
-      // self-tagged hand-off (fp32 partials through the L2 ring): the two ring
-      // images start with tag 1 in every word (steps 0 and 1 publish tag 0)
-      p.dtag = d.prec != kPrecBf16 && p.ring == 2 && p.xpd && T >= 2;
-      if (p.dtag)
-        KCTC_HIP_CHECK(hipMemsetAsync(p.xch, 0x01, sizeof(float) * 2 * (size_t)dirs * p.nwg * (16 * H + 64) * p.rg, s));
-    } else {
-      p.xch = reinterpret_cast<float *>(static_cast<char *>(workspace) + xch_offset(d, T, N));
-    }
-    const dim3 grid(ver == 4 ? 8 * ceil_div(p.nwg, p.xpd) : ver == 6 && p.xpd ? 8 * p.nwg : dirs * p.nwg * p.rg);
-    RecTrace tr;
-    if (tr.arm("bwd", grid.x)) p.trace = tr.dev;
+    if (pl.ver == 3) KCTC_HIP_CHECK(hipMemsetAsync(E, 0xFF, sizeof(float) * TN * dirs * NW * H, s));
+    RecParams p = rec_params(d, pl, ws, T, N, wl, lw, R0, lay, const_cast<float *>(out), err, s);
     // dx_l = sum_dir DX_dir W_dir   (lower layer's dy, or the caller's dx)
     float *dxl = (l == 0) ? dx : res + lay.per_layer * (l - 1) + lay.dout;
     // streamed: computed on `overlap` while the recurrence runs, from its rows as they appear
-    const bool streamed = dxl && overlap && ver == 6 && bwd_dx_stream_ok(d, l, T, N);
+    const bool streamed = dxl && overlap && v6 && bwd_dx_stream_ok(pl, d, l, T, N);
     // weight gradients streamed off this recurrence (the bottom component):
     // its dGates rows must be written through too
-    const bool wstream = wgrad && wgrad->side && !dxl && ver == 6 && !p.xpd && d.layers == 1 &&
-                         rnn_wgrad_stream_ok(d, T, N);
-    p.e_sc1 = (streamed || wstream) ? 1 : 0;
-    // bf16: dGates straight into the packed operands of the dx / dW / dR GEMMs
-    // (no fp32 rows, no pack passes over them; KCTC_BF16_DIRECT=0: the fp32
-    // rows and the pack kernels as in round 3)
-    const bool pkd = bf16_direct(d, ver);  // beside e_sc1's write-through rows when streamed
-    if (pkd) {
-      p.dxr = reinterpret_cast<__bf16 *>(R0 + lay.pkxr);
-      p.dxt = reinterpret_cast<__bf16 *>(R0 + lay.pkxt);
-      p.eshift = bf16_io(d) ? 1 : 0;
-      p.et = (d.mode == kGru || p.eshift) ? reinterpret_cast<__bf16 *>(R0 + lay.pket) : p.dxt;
-      p.kbt64 = lay.kbt64;
-      const size_t pitch = sizeof(__bf16) * lay.kbt64;
-      const size_t rows = (size_t)NW * H;  // per direction
-      if (lay.kbt64 > TN)  // the frame tail of every packed row stays zero
-        KCTC_HIP_CHECK(hipMemset2DAsync(p.dxt + TN, pitch, 0, sizeof(__bf16) * (lay.kbt64 - TN), dirs * rows, s));
-      if (p.eshift) {  // E^T shifted: direction 0 from TN - N on, direction 1 before N and from TN on
-        KCTC_HIP_CHECK(hipMemset2DAsync(p.et + TN - N, pitch, 0, sizeof(__bf16) * (lay.kbt64 - TN + N), rows, s));
-        KCTC_HIP_CHECK(hipMemset2DAsync(p.et + rows * lay.kbt64, pitch, 0, sizeof(__bf16) * N, rows, s));
-        if (lay.kbt64 > TN)
-          KCTC_HIP_CHECK(hipMemset2DAsync(p.et + rows * lay.kbt64 + TN, pitch, 0, sizeof(__bf16) * (lay.kbt64 - TN),
-                                          rows, s));
-      } else if (d.mode == kGru && lay.kbt64 > TN) {
-        KCTC_HIP_CHECK(hipMemset2DAsync(p.et + TN, pitch, 0, sizeof(__bf16) * (lay.kbt64 - TN), dirs * rows, s));
-      }
-    }
-    if (ver == 6) {
-      p.cmax = pk<unsigned>(workspace, d, T, N, pack_layout(d, T, N).cme);
-      if (p.rg > 1)  // max over the row groups by atomicMax on the float bits
-        KCTC_HIP_CHECK(hipMemsetAsync(p.cmax, 0, sizeof(unsigned) * 2 * dirs * NW * H, s));
-    }
+    const bool wstream = wgrad && wgrad->side && !dxl && v6 && !p.xpd && d.layers == 1 &&
+                         wgrad_stream_shape(d, T, N) && wgrad_stream_ok(pl, d, T, N);
+    bwd_rec_params(p, d, pl, ws, R0, lay, dcur, E, DX, streamed || wstream, s);
     const hipEvent_t fork = (streamed || wstream) ? fork_event(s) : nullptr;
     RegWord &rw = reg_of_device();
-    if (ver == 6) p.reg = rw.word;  // registration for the exchange's residency gate
-    {
-      ProfSpan ps(s, "rnn_bwd_rec");
-      if (ver == 6) launch_rec(rec6_kernel(false, d.mode, d.prec, H, c6), p, grid, c6.nth, lds, s);
-      else launch_rec(rec_generic_kernel(false, ver, d.mode, p.Npad / 16), p, grid, NT, lds, s);
-    }
-    KCTC_HIP_CHECK(hipGetLastError());
-    if (ver == 6) {
-      // counted once the launch is enqueued (a failed launch never raises the target)
-      rw.expected += (unsigned long long)(dirs * p.nwg * p.rg);
-      rec_scope.enqueued(p);
-      g_last_bwd_scratch_free = rec6_scratch_free(d, N, false);
-    } else {
-      rec_scope.none();
-      g_last_bwd_scratch_free = true;
-    }
+    if (v6) p.reg = rw.word;  // registration for the exchange's residency gate
+    RecTrace tr;
+    launch_planned(d, pl, false, p, tr, rec_scope, s);
+    // counted once the launch is enqueued (a failed launch never raises the target)
+    if (v6) rw.expected += (unsigned long long)pl.wgs;
+    g_last_bwd_scratch_free = v6 ? pl.scratch_free : true;
     if (streamed) {
-      launch_bwd_stream(d, p, l, w, dxl, workspace, T, N, overlap, fork, err, d.layers == 1 ? pre : nullptr);
+      launch_bwd_stream(d, p, l, w, dxl, ws, T, N, overlap, fork, err, d.layers == 1 ? pre : nullptr);
       join_stream(s, overlap);
     }
-    if (wstream) {
-      // chunk c of C: direction 0 frames [T - b(c+1), T - b(c)), direction 1
-      // [b(c), b(c+1)), b(c) = c T / C; complete once every flag line holds
-      // epoch b(c+1) + 2 (rows of step k are out at epoch k + 3)
-      hipStream_t ws2 = wgrad->side;
-      KCTC_HIP_CHECK(hipStreamWaitEvent(ws2, fork, 0));  // after the flag reset
-      beside_recurrence(ws2);
-      const int C = std::max(1, std::min(wgrad->chunks, T / 4));
-      const unsigned *lines = p.flags + 1024;
-      const int nlines = p.rg * dirs * p.nwg;
-      for (int c = 0; c < C; c++) {
-        const int b0 = (int)((long)c * T / C), b1 = (int)((long)(c + 1) * T / C);
-        hipLaunchKernelGGL(rec_gate_kernel, dim3(1), dim3(64), 0, ws2, lines, nlines, (unsigned)(b1 + 2), err);
-        wgrad_frames(d, ws2, T, N, wgrad->x, y, workspace, wgrad->dw, reserve, wgrad->max_blocks, wgrad->in_bound, 0,
-                     T - b1, T - b0);
-        wgrad_frames(d, ws2, T, N, wgrad->x, y, workspace, wgrad->dw, reserve, wgrad->max_blocks, wgrad->in_bound, 1,
-                     b0, b1);
-      }
-      join_stream(ws2, s);  // the bias partials are written after the last flag
-      wgrad_bias(d, ws2, T, N, wgrad->dw, reserve, 0);
-      wgrad->done = true;
-    }
-    if (ver == 6) xch_release(s);
-    tr.dump("bwd", s, grid.x, p.nwg, T, dirs, ver, ver == 6 ? (p.xpd ? 1 : 0) : p.xpd);
-    if (dxl && !streamed && d.prec == kPrecBf16 && use_x3(NW * H)) {
-      // bf16: dGates rows and W^T rows (columns of W) packed as bf16 (the
-      // dGates rows written packed by the recurrence when pkd)
-      const long G4 = (long)NW * H;
-      const int KB = (int)((G4 + 63) / 64);
-      const PackLay pl = pack_layout(d, T, N);
-      __bf16 *Ap = pkd ? p.dxr : pk<__bf16>(workspace, d, T, N, pl.a), *Bp = pk<__bf16>(workspace, d, T, N, pl.b);
-      {
-        ProfSpan ps(s, "x3_pack");
-        if (!pkd) bf16_pack_rows(s, DX, (long)dirs * G4, (int)TN, (int)G4, Ap, dirs, G4, TN * KB * 64);
-        for (int dir = 0; dir < dirs; dir++)
-          bf16_pack_cols(s, wl + dir * pls, Din, (int)G4, Din, 0, Bp + (long)dir * Din * KB * 64);
-      }
-      for (int dir = 0; dir < dirs; dir++) {
-        ProfSpan ps(s, "gemm_bwd_data");
-        X3PArgs x;
-        x.bf16 = true;
-        x.M = (int)TN; x.N = Din; x.KB = KB;
-        x.A = reinterpret_cast<const _Float16 *>(Ap + (long)dir * TN * KB * 64);
-        x.B = reinterpret_cast<const _Float16 *>(Bp + (long)dir * Din * KB * 64);
-        x.C = dxl; x.ldc = Din; x.beta = dir == 0 ? 0.f : 1.f;
-        gemm_x3p(s, x);
-      }
-    } else if (dxl && !streamed) {
-      const bool x3 = use_x3(NW * H);
-      const long G4 = (long)NW * H;
-      const int KB = (int)((G4 + 31) / 32);
-      const PackLay pl = pack_layout(d, T, N);
-      _Float16 *Ap = pk<_Float16>(workspace, d, T, N, pl.a), *Bp = pk<_Float16>(workspace, d, T, N, pl.b);
-      int *eA = pk<int>(workspace, d, T, N, pl.ea), *eB = pk<int>(workspace, d, T, N, pl.eb);
-      unsigned *cm = pk<unsigned>(workspace, d, T, N, pl.cm);
-      if (x3) {
-        // dGates rows (frames, per direction) and W^T rows (input dims), packed over the gates
-        ProfSpan ps(s, "x3_pack");
-        x3p_pack_rows(s, DX, (long)dirs * G4, (int)TN, (int)G4, Ap, eA, 0.f, dirs, G4, TN * KB * 64, TN);
-        for (int dir = 0; dir < dirs; dir++) {
-          absmax_f32(s, wl + dir * pls, Din, (int)G4, Din, nullptr, cm);
-          x3p_pack_cols(s, wl + dir * pls, Din, (int)G4, Din, 0, Bp + (long)dir * Din * KB * 64, eB + dir * Din, cm,
-                        0.f);
-        }
-      }
-      for (int dir = 0; dir < dirs; dir++) {
-        ProfSpan ps(s, "gemm_bwd_data");
-        if (x3) {
-          X3PArgs x;
-          x.M = (int)TN; x.N = Din; x.KB = KB;
-          x.A = Ap + (long)dir * TN * KB * 64; x.eA = eA + (long)dir * TN;
-          x.B = Bp + (long)dir * Din * KB * 64; x.eB = eB + dir * Din;
-          x.C = dxl; x.ldc = Din; x.beta = dir == 0 ? 0.f : 1.f;
-          gemm_x3p(s, x);
-        } else {
-          GemmArgs g;
-          g.transA = false; g.transB = false;
-          g.M = (int)TN; g.N = Din; g.K = NW * H;
-          g.A = DX + (long)dir * NW * H; g.lda = (long)dirs * NW * H;
-          g.B = wl + dir * pls; g.ldb = Din;
-          g.C = dxl; g.ldc = Din;
-          g.beta = dir == 0 ? 0.f : 1.f;
-          gemm_f32(s, g);
-        }
-      }
-    }
+    if (wstream) launch_wgrad_stream(pl, d, p, fork, T, N, y, ws, reserve, err, *wgrad, s);
+    if (v6) xch_release(s);
+    tr.dump("bwd", s, pl.grid, p.nwg, T, dirs, pl.ver, p.xpd);
+    if (dxl && !streamed) dx_gemm(d, ws, s, TN, l, DX, p.dxr, wl, lw.pls, dxl);
     dcur = dxl;
   }
   return KRNN_OK;
@@ -1561,266 +1063,310 @@ int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float
 // ---------------------------------------------------------------------------
 // host: backward weights (accumulates into dw, like cudnnRNNBackwardWeights)
 // ---------------------------------------------------------------------------
+namespace {
+// One stacked layer of rnn_backward_weights: dW_dir += DX_dir^T in and
+// dR_dir += E_dir(shifted)^T h_prev -- direction 0 pairs rows t >= 1 with out
+// rows t - 1, direction 1 rows t <= T - 2 with out rows t + 1
+struct WgradLayer {
+  const RnnDesc &d;
+  const RnnWs &ws;
+  hipStream_t s;
+  int T, N, l;
+  const float *in, *out;  // the layer's input and output rows
+  float *E, *DX;          // dGates (recurrent / input part; the same but for a GRU)
+  float *dwl;             // the layer's gradient block
+  long pls, roff;         // LayerW
+  int max_blocks;
+  long TN() const { return (long)T * N; }
+  long G4() const { return (long)d.nw() * d.H; }
+};
+
+// bf16 weight GEMMs: the transposes packed along the frames as bf16
+void wgrad_bf16(const WgradLayer &g, float *R0, const RnnReserveLayout &lay, const void *in_cols) {
+  const RnnDesc &d = g.d;
+  const RnnWs &ws = g.ws;
+  hipStream_t s = g.s;
+  const int H = d.H, dirs = d.dirs, Din = d.din(g.l), N = g.N;
+  const long TN = g.TN(), G4 = g.G4(), ldg = dirs * G4, ldy = (long)dirs * H;
+  const int KB = (int)((TN + 63) / 64);
+  // the dGates transposes: written packed by the backward recurrence (bf16_direct)
+  const bool pkd = bf16_direct(d, 6);
+  // bf16_io: the forward wrote y^T packed (unshifted) and the backward
+  // E^T shifted by one step; the input's columns may come packed from the
+  // previous component's forward (in_cols)
+  const bool io = bf16_io(d);
+  const bool cols_in = g.l == 0 && in_cols != nullptr;
+  __bf16 *DXt = pkd ? reinterpret_cast<__bf16 *>(R0 + lay.pkxt) : ws.at<__bf16>(ws.lay.a);
+  __bf16 *Xt = cols_in ? static_cast<__bf16 *>(const_cast<void *>(in_cols)) : ws.at<__bf16>(ws.lay.b);
+  __bf16 *Yt = io ? reinterpret_cast<__bf16 *>(R0 + lay.pkyc) : ws.at<__bf16>(ws.lay.c);
+  __bf16 *Et = (d.mode == kGru || io)
+                   ? (pkd ? reinterpret_cast<__bf16 *>(R0 + lay.pket) : DXt + (long)dirs * G4 * KB * 64)
+                   : DXt;
+  {
+    ProfSpan ps(s, "x3_pack_w");
+    if (!pkd) {
+      bf16_pack_cols(s, g.DX, ldg, (int)TN, (int)(dirs * G4), 0, DXt);
+      if (d.mode == kGru) bf16_pack_cols(s, g.E, ldg, (int)TN, (int)(dirs * G4), 0, Et);
+    }
+    if (!cols_in) bf16_pack_cols(s, g.in, Din, (int)TN, Din, 0, Xt);
+    if (g.T > 1 && !io)
+      for (int dir = 0; dir < dirs; dir++)
+        bf16_pack_cols(s, g.out + (long)dir * H, ldy, (int)TN, H, dir == 0 ? N : -N, Yt + (long)dir * H * KB * 64);
+  }
+  {
+    X3PArgs x;
+    x.bf16 = true;
+    x.M = (int)G4; x.N = Din; x.KB = KB;
+    x.A = reinterpret_cast<const _Float16 *>(DXt); x.sA = G4 * KB * 64;
+    x.B = reinterpret_cast<const _Float16 *>(Xt);
+    x.C = g.dwl; x.ldc = Din; x.beta = 1.f;
+    x.batch = dirs; x.sC = g.pls;
+    x.split_k = x3p_pick_split((int)G4, Din, KB, dirs); x.ws = ws.split_slab();
+    x.max_blocks = g.max_blocks; x.tile_counter = tile_counter(ws, kTileWordW, g.max_blocks);
+    ProfSpan ps(s, "gemm_bwd_w");
+    gemm_x3p(s, x);
+  }
+  if (g.T > 1) {
+    X3PArgs x;
+    x.bf16 = true;
+    x.M = (int)G4; x.N = H; x.KB = KB;
+    x.A = reinterpret_cast<const _Float16 *>(Et); x.sA = G4 * KB * 64;
+    x.B = reinterpret_cast<const _Float16 *>(Yt); x.sB = (long)H * KB * 64;
+    x.C = g.dwl + g.roff; x.ldc = H; x.beta = 1.f;
+    x.batch = dirs; x.sC = g.pls;
+    x.split_k = x3p_pick_split((int)G4, H, KB, dirs); x.ws = ws.split_slab();
+    x.max_blocks = g.max_blocks; x.tile_counter = tile_counter(ws, kTileWordR, g.max_blocks);
+    ProfSpan ps(s, "gemm_bwd_r");
+    gemm_x3p(s, x);
+  }
+}
+
+// fp32 weight GEMMs (few frames)
+void wgrad_f32(const WgradLayer &g) {
+  const RnnDesc &d = g.d;
+  const int H = d.H, dirs = d.dirs, Din = d.din(g.l), N = g.N, G4 = (int)g.G4();
+  const long ldg = (long)dirs * G4, ldy = (long)dirs * H;
+  {
+    GemmArgs w;
+    w.transA = true; w.transB = false;
+    w.M = G4; w.N = Din; w.K = (int)g.TN();
+    w.A = g.DX; w.lda = ldg; w.B = g.in; w.ldb = Din;
+    w.C = g.dwl; w.ldc = Din; w.beta = 1.f;
+    w.batch = dirs; w.strideA = G4; w.strideB = 0; w.strideC = g.pls;
+    w.split_k = gemm_pick_split(w.M, w.N, w.K, dirs);
+    w.ws = g.ws.split_slab();
+    w.max_blocks = g.max_blocks;
+    w.tile_counter = tile_counter(g.ws, kTileWordW, g.max_blocks);
+    ProfSpan ps(g.s, "gemm_bwd_w");
+    gemm_f32(g.s, w);
+  }
+  if (g.T > 1) {
+    GemmArgs r;
+    r.transA = true; r.transB = false;
+    r.M = G4; r.N = H; r.K = (int)((long)(g.T - 1) * N);
+    r.A = g.E + (long)N * ldg; r.lda = ldg;
+    r.B = g.out; r.ldb = ldy;
+    r.C = g.dwl + g.roff; r.ldc = H; r.beta = 1.f;
+    r.batch = dirs;
+    r.strideA = (long)G4 - (long)N * ldg;        // dir 1: E + G4 (rows 0..T-2)
+    r.strideB = (long)N * ldy + H;               // dir 1: y rows 1..T-1, cols H..
+    r.strideC = g.pls;
+    r.split_k = gemm_pick_split(r.M, r.N, r.K, dirs);
+    r.ws = g.ws.split_slab();
+    r.max_blocks = g.max_blocks;
+    r.tile_counter = tile_counter(g.ws, kTileWordR, g.max_blocks);
+    ProfSpan ps(g.s, "gemm_bwd_r");
+    gemm_f32(g.s, r);
+  }
+}
+
+// The packed operands of wgrad_x3: dGates^T (per-gate exponents), input^T
+// (per-dim), the output^T shifted by one step per direction, E^T (GRU; else
+// dGates^T again), each with its exponents
+struct WgradCols {
+  _Float16 *DXt, *Xt, *Yt, *Et;
+  int *eDX, *eX, *eY, *eE;
+  const unsigned *cme;  // the dGates column maxima a v6 backward recurrence left behind (else null)
+  bool wpre;            // x^T and y^T came packed from the forward (RnnPrepack::wgrad)
+};
+
+// Two streams (s2, the bottom component's tail, where nothing else overlaps):
+// input^T and output^T are packed (and dW then runs) on s2 while dGates^T is
+// packed (and dR runs) on s: separate split slabs, tile counters and absmax
+// scratch.  (LSTM: dR's dGates^T is dW's, E == DX.)
+void pack_wgrad_two(const WgradLayer &g, const WgradCols &c, float in_bound, hipStream_t s2, hipEvent_t ev_dx,
+                    hipEvent_t ev_y) {
+  const RnnDesc &d = g.d;
+  hipStream_t s = g.s;
+  const int H = d.H, dirs = d.dirs, Din = d.din(g.l), N = g.N;
+  const long TN = g.TN(), G4 = g.G4(), ldy = (long)dirs * H, KBt = (TN + 31) / 32;
+  ProfSpan ps(s, "x3_pack_w");
+  x3p_pack_cols(s, g.DX, dirs * G4, (int)TN, (int)(dirs * G4), 0, c.DXt, c.eDX, c.cme, 0.f);
+  KCTC_HIP_CHECK(hipEventRecord(ev_dx, s));
+  const bool xb = g.l == 0 && in_bound > 0.f;
+  // absmax scratch of its own: the GRU-only E^T exponent array (free for an LSTM)
+  unsigned *cmx = reinterpret_cast<unsigned *>(g.ws.at<int>(g.ws.lay.ed));
+  if (!c.wpre) {
+    if (!xb) absmax_f32(s2, g.in, Din, (int)TN, Din, nullptr, cmx);
+    x3p_pack_cols(s2, g.in, Din, (int)TN, Din, 0, c.Xt, c.eX, cmx, xb ? in_bound : 0.f);
+    for (int dir = 0; dir < dirs; dir++)
+      x3p_pack_cols(s2, g.out + (long)dir * H, ldy, (int)TN, H, dir == 0 ? N : -N, c.Yt + (long)dir * H * KBt * 64,
+                    c.eY + dir * H, nullptr, 1.f);
+  }
+  KCTC_HIP_CHECK(hipEventRecord(ev_y, s2));
+  KCTC_HIP_CHECK(hipStreamWaitEvent(s2, ev_dx, 0));
+  KCTC_HIP_CHECK(hipStreamWaitEvent(s, ev_y, 0));
+}
+
+// One stream; beside another component's pinned recurrence the packs keep off its XCDs
+void pack_wgrad_one(const WgradLayer &g, const WgradCols &c, float in_bound, bool beside) {
+  const RnnDesc &d = g.d;
+  const RnnWs &ws = g.ws;
+  hipStream_t s = g.s;
+  const int H = d.H, dirs = d.dirs, Din = d.din(g.l), N = g.N, l = g.l;
+  const long TN = g.TN(), G4 = g.G4(), ldg = dirs * G4, ldy = (long)dirs * H, KBt = (TN + 31) / 32;
+  unsigned *cm = ws.at<unsigned>(ws.lay.cm);
+  ProfSpan ps(s, "x3_pack_w");
+  // (x3p_pack_cols avoid)
+  const unsigned *av = beside ? rnn_pinned_xcds() : nullptr;
+  const int nx = std::max(1, rnn_usable_cus() / kCusPerXcd);
+  // their item counters: flag words kPackWord.. (this component's
+  // recurrences, which use the flag words, are done)
+  int *pc = reinterpret_cast<int *>(ws.flags() + kPackWord);
+  if (av) KCTC_HIP_CHECK(hipMemsetAsync(pc, 0, sizeof(int) * kPackWords, s));
+  if (!c.cme) absmax_f32(s, g.DX, ldg, (int)TN, (int)(dirs * G4), nullptr, cm);
+  x3p_pack_cols(s, g.DX, ldg, (int)TN, (int)(dirs * G4), 0, c.DXt, c.eDX, c.cme ? c.cme : cm, 0.f, 1, 0, 0, 0, 0, av,
+                nx, pc);
+  if (d.mode == kGru) {
+    if (!c.cme) absmax_f32(s, g.E, ldg, (int)TN, (int)(dirs * G4), nullptr, cm);
+    x3p_pack_cols(s, g.E, ldg, (int)TN, (int)(dirs * G4), 0, c.Et, c.eE, c.cme ? c.cme + dirs * G4 : cm, 0.f, 1, 0, 0,
+                  0, 0, av, nx, pc + 1);
+  }
+  if (c.wpre) return;
+  const bool xb = (l > 0 && bounded_out(d)) || (l == 0 && in_bound > 0.f);
+  if (!xb) absmax_f32(s, g.in, Din, (int)TN, Din, nullptr, cm);
+  x3p_pack_cols(s, g.in, Din, (int)TN, Din, 0, c.Xt, c.eX, cm, xb ? (l > 0 ? 1.f : in_bound) : 0.f, 1, 0, 0, 0, 0, av,
+                nx, pc + 2);
+  if (g.T > 1) {
+    if (!bounded_out(d)) absmax_f32(s, g.out, ldy, (int)TN, (int)ldy, nullptr, cm);
+    for (int dir = 0; dir < dirs; dir++)
+      x3p_pack_cols(s, g.out + (long)dir * H, ldy, (int)TN, H, dir == 0 ? N : -N, c.Yt + (long)dir * H * KBt * 64,
+                    c.eY + dir * H, bounded_out(d) ? nullptr : cm + dir * H, bounded_out(d) ? 1.f : 0.f, 1, 0, 0, 0,
+                    0, av, nx, pc + 3 + dir);
+  }
+}
+
+// split-fp16 weight GEMMs on operands packed over the frames (all frames: the
+// shifted-out ones are zero in the packed output^T).  v6b: the layer's
+// backward ran v6.
+void wgrad_x3(const WgradLayer &g, bool v6b, float in_bound, hipStream_t s2, bool beside, const RnnPrepack *pre) {
+  const RnnDesc &d = g.d;
+  const RnnWs &ws = g.ws;
+  const PackLay &pl = ws.lay;
+  hipStream_t s = g.s;
+  const int H = d.H, dirs = d.dirs, Din = d.din(g.l), T = g.T;
+  const long TN = g.TN(), G4 = g.G4();
+  const int KBt = (int)((TN + 31) / 32);
+  WgradCols c;
+  // x^T and y^T packed by the forward, else here
+  c.wpre = pre && pre->wdone && pre->wev && d.layers == 1 && T > 1;
+  c.DXt = ws.at<_Float16>(pl.a);
+  c.Xt = ws.at<_Float16>(c.wpre ? pl.xt : pl.b);
+  c.Yt = ws.at<_Float16>(c.wpre ? pl.yt : pl.c);
+  c.Et = d.mode == kGru ? c.DXt + (long)dirs * G4 * KBt * 64 : c.DXt;
+  c.eDX = ws.at<int>(pl.ea);
+  c.eX = ws.at<int>(c.wpre ? pl.ext : pl.eb);
+  c.eY = ws.at<int>(c.wpre ? pl.eyt : pl.ec);
+  c.eE = d.mode == kGru ? ws.at<int>(pl.ed) : c.eDX;
+  c.cme = v6b ? ws.at<unsigned>(pl.cme) : nullptr;
+  if (c.wpre) KCTC_HIP_CHECK(hipStreamWaitEvent(s, pre->wev, 0));
+  // (the GRU's E^T pack stays on one stream)
+  const bool two = s2 && c.cme && d.mode == kLstm && d.layers == 1 && T > 1 && env_int("KCTC_WGRAD_2S", 1);
+  hipStream_t sx = two ? s2 : s;  // stream of the input / output packs and of dW
+  hipEvent_t ev_dx = nullptr, ev_y = nullptr;
+  if (two) {
+    KCTC_HIP_CHECK(hipEventCreateWithFlags(&ev_dx, hipEventDisableTiming));
+    KCTC_HIP_CHECK(hipEventCreateWithFlags(&ev_y, hipEventDisableTiming));
+    join_stream(s2, s);
+    pack_wgrad_two(g, c, in_bound, s2, ev_dx, ev_y);
+  } else {
+    pack_wgrad_one(g, c, in_bound, beside);
+  }
+  // beside another component's pinned backward recurrence: dW and dR as
+  // one launch on the CUs it leaves (gemm_x3p_pair; configs[1]: the side
+  // stream fell one GEMM per layer behind, 4 ms of weight GEMMs after the
+  // last recurrence)
+  const bool pair = beside && !two && T > 1 && x3p_use_256((int)G4, Din) && x3p_use_256((int)G4, H) &&
+                    g.max_blocks > 0;
+  X3PArgs xw;
+  xw.M = (int)G4; xw.N = Din; xw.KB = KBt;
+  xw.A = c.DXt; xw.eA = c.eDX; xw.sA = G4 * KBt * 64; xw.seA = G4;
+  xw.B = c.Xt; xw.eB = c.eX;
+  xw.C = g.dwl; xw.ldc = Din; xw.beta = 1.f;
+  xw.batch = dirs; xw.sC = g.pls;
+  xw.split_k = x3p_pick_split((int)G4, Din, KBt, dirs);
+  // concurrent with dR: its own split slab past dR's (none when dR is not
+  // split: the slabs reserve room for dR only for a split > 1)
+  const long sR = x3p_pick_split((int)G4, H, KBt, dirs);
+  xw.ws = (two || pair) && sR > 1 ? ws.split_slab() + (sR * dirs * G4 * H + 63) / 64 * 64 : ws.split_slab();
+  xw.max_blocks = g.max_blocks; xw.tile_counter = tile_counter(ws, kTileWordW, g.max_blocks);
+  if (pair) {
+    xw.max_blocks = 192;
+    xw.avoid_word = rnn_pinned_xcds();
+    xw.avoid_xcds = std::max(1, rnn_usable_cus() / kCusPerXcd);
+  } else {
+    ProfSpan ps(sx, "gemm_bwd_w");
+    gemm_x3p(sx, xw);
+  }
+  if (T > 1) {
+    ProfSpan ps(s, "gemm_bwd_r");
+    X3PArgs x;
+    x.M = (int)G4; x.N = H; x.KB = KBt;
+    x.A = c.Et; x.eA = c.eE; x.sA = G4 * KBt * 64; x.seA = G4;
+    x.B = c.Yt; x.eB = c.eY; x.sB = (long)H * KBt * 64; x.seB = H;
+    x.C = g.dwl + g.roff; x.ldc = H; x.beta = 1.f;
+    x.batch = dirs; x.sC = g.pls;
+    x.split_k = x3p_pick_split((int)G4, H, KBt, dirs); x.ws = ws.split_slab();
+    x.max_blocks = g.max_blocks; x.tile_counter = tile_counter(ws, kTileWordR, g.max_blocks);
+    if (pair) gemm_x3p_pair(s, xw, x);  // xw's tile counter, block count and avoid word
+    else gemm_x3p(s, x);
+  }
+  if (two) {
+    join_stream(s, s2);
+    (void)hipEventDestroy(ev_dx);
+    (void)hipEventDestroy(ev_y);
+  }
+}
+}  // namespace
+
 int rnn_backward_weights(const RnnDesc &d, hipStream_t s, int T, int N, const float *x,
                          const float *y, void *workspace, size_t ws_bytes, float *dw,
                          void *reserve, size_t res_bytes, int max_blocks, float in_bound, hipStream_t s2,
                          const void *in_cols, bool beside, const RnnPrepack *pre) {
   const RnnReserveLayout lay = rnn_reserve_layout(d, T, N);
   if (res_bytes < sizeof(float) * (size_t)lay.total) return KRNN_BAD_PARAM;
-  if (ws_bytes < rnn_workspace_bytes(d, T, N)) return KRNN_BAD_PARAM;
-  const int NW = d.nw(), H = d.H, dirs = d.dirs, G4 = NW * H;
-  const long TN = (long)T * N;
+  const RnnWs ws(d, T, N, workspace);
+  if (ws_bytes < ws.bytes()) return KRNN_BAD_PARAM;
+  const RecPlan plb = plan_rec(d, N, false);  // the backward recurrence that left dGates and bias partials
   float *res = static_cast<float *>(reserve);
-  float *ws = static_cast<float *>(workspace);
+  // K = frames: large (also for a 40-dim input: 0.8 ms/step over fp32).
+  // A bf16 backward that wrote its dGates packed (bf16_direct) left no fp32
+  // rows: its packed operands are the only ones, however few the frames
+  // (under 128 frames the fp32 GEMMs would read rows nobody had written)
+  const bool x3 = use_x3((int)((long)T * N)) || bf16_direct(d, 6);
   for (int l = 0; l < d.layers; l++) {
     float *R0 = res + lay.per_layer * l;
-    const float *in = l == 0 ? x : res + lay.per_layer * (l - 1) + lay.out;
-    const float *out = (l == d.layers - 1) ? y : R0 + lay.out;
-    const int Din = d.din(l);
-    const long pl0 = d.lin_offset(l * dirs, 0, false);
-    const long pls = d.pl_size(l);
-    float *dwl = dw + pl0;
+    const LayerW lw = layer_w(d, l);
     float *E = R0 + lay.E;
-    float *DX = d.mode == kGru ? R0 + lay.DX : E;
-    const long ldg = (long)dirs * G4, ldy = (long)dirs * H;
-    // dW_dir += DX_dir^T x
-    GemmArgs g;
-    g.transA = true; g.transB = false;
-    g.M = G4; g.N = Din; g.K = (int)TN;
-    g.A = DX; g.lda = ldg; g.B = in; g.ldb = Din;
-    g.C = dwl; g.ldc = Din; g.beta = 1.f;
-    g.batch = dirs; g.strideA = G4; g.strideB = 0; g.strideC = pls;
-    g.split_k = gemm_pick_split(g.M, g.N, g.K, dirs);
-    g.ws = ws;
-    g.max_blocks = max_blocks;
-    // flag words 1008..1009 of the workspace: dynamic tile counters (the
-    // recurrences of this layer, which use the other flag words, are done)
-    unsigned *fl = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + flags_offset(d, T, N));
-    if (max_blocks > 0) g.tile_counter = reinterpret_cast<int *>(fl + 1008);
-    // K = frames: large (also for a 40-dim input: 0.8 ms/step over fp32).
-    // A bf16 backward that wrote its dGates packed (bf16_direct) left no fp32
-    // rows: its packed operands are the only ones, however few the frames
-    // (under 128 frames the fp32 GEMMs below read rows nobody had written)
-    const bool x3 = use_x3((int)TN) || bf16_direct(d, 6);
-    if (x3 && d.prec == kPrecBf16) {
-      // bf16 weight GEMMs: the transposes packed along the frames as bf16
-      const int KB = (int)((TN + 63) / 64);
-      const PackLay pl = pack_layout(d, T, N);
-      // the dGates transposes: written packed by the backward recurrence (bf16_direct)
-      const bool pkd = bf16_direct(d, 6);
-      // bf16_io: the forward wrote y^T packed (unshifted) and the backward
-      // E^T shifted by one step; the input's columns may come packed from the
-      // previous component's forward (in_cols)
-      const bool io = bf16_io(d);
-      const bool cols_in = l == 0 && in_cols != nullptr;
-      __bf16 *DXt = pkd ? reinterpret_cast<__bf16 *>(R0 + lay.pkxt) : pk<__bf16>(workspace, d, T, N, pl.a);
-      __bf16 *Xt = cols_in ? static_cast<__bf16 *>(const_cast<void *>(in_cols)) : pk<__bf16>(workspace, d, T, N, pl.b);
-      __bf16 *Yt = io ? reinterpret_cast<__bf16 *>(R0 + lay.pkyc) : pk<__bf16>(workspace, d, T, N, pl.c);
-      __bf16 *Et = (d.mode == kGru || io)
-                       ? (pkd ? reinterpret_cast<__bf16 *>(R0 + lay.pket) : DXt + (long)dirs * G4 * KB * 64)
-                       : DXt;
-      {
-        ProfSpan ps(s, "x3_pack_w");
-        if (!pkd) {
-          bf16_pack_cols(s, DX, ldg, (int)TN, (int)(dirs * G4), 0, DXt);
-          if (d.mode == kGru) bf16_pack_cols(s, E, ldg, (int)TN, (int)(dirs * G4), 0, Et);
-        }
-        if (!cols_in) bf16_pack_cols(s, in, Din, (int)TN, Din, 0, Xt);
-        if (T > 1 && !io)
-          for (int dir = 0; dir < dirs; dir++)
-            bf16_pack_cols(s, out + (long)dir * H, ldy, (int)TN, H, dir == 0 ? N : -N, Yt + (long)dir * H * KB * 64);
-      }
-      {
-        X3PArgs x;
-        x.bf16 = true;
-        x.M = (int)G4; x.N = Din; x.KB = KB;
-        x.A = reinterpret_cast<const _Float16 *>(DXt); x.sA = G4 * KB * 64;
-        x.B = reinterpret_cast<const _Float16 *>(Xt);
-        x.C = dwl; x.ldc = Din; x.beta = 1.f;
-        x.batch = dirs; x.sC = pls;
-        x.split_k = x3p_pick_split((int)G4, Din, KB, dirs); x.ws = ws;
-        x.max_blocks = g.max_blocks; x.tile_counter = g.tile_counter;
-        ProfSpan ps(s, "gemm_bwd_w");
-        gemm_x3p(s, x);
-      }
-      if (T > 1) {
-        X3PArgs x;
-        x.bf16 = true;
-        x.M = (int)G4; x.N = H; x.KB = KB;
-        x.A = reinterpret_cast<const _Float16 *>(Et); x.sA = G4 * KB * 64;
-        x.B = reinterpret_cast<const _Float16 *>(Yt); x.sB = (long)H * KB * 64;
-        x.C = dwl + (d.lin_offset(l * dirs, NW, false) - pl0); x.ldc = H; x.beta = 1.f;
-        x.batch = dirs; x.sC = pls;
-        x.split_k = x3p_pick_split((int)G4, H, KB, dirs); x.ws = ws;
-        x.max_blocks = max_blocks;
-        if (max_blocks > 0) x.tile_counter = reinterpret_cast<int *>(fl + 1009);
-        ProfSpan ps(s, "gemm_bwd_r");
-        gemm_x3p(s, x);
-      }
-    }
-    if (x3 && d.prec == kPrecBf16) {
-    } else {
-    const int KBt = (int)((TN + 31) / 32);
-    const PackLay pl = pack_layout(d, T, N);
-    // x^T and y^T packed by the forward (RnnPrepack::wgrad), else here
-    const bool wpre = pre && pre->wdone && pre->wev && use_x3((int)TN) && d.layers == 1 && T > 1;
-    _Float16 *DXt = pk<_Float16>(workspace, d, T, N, pl.a);
-    _Float16 *Xt = pk<_Float16>(workspace, d, T, N, wpre ? pl.xt : pl.b);
-    _Float16 *Yt = pk<_Float16>(workspace, d, T, N, wpre ? pl.yt : pl.c);
-    _Float16 *Et = d.mode == kGru ? DXt + (long)dirs * G4 * KBt * 64 : DXt;
-    int *eDX = pk<int>(workspace, d, T, N, pl.ea), *eX = pk<int>(workspace, d, T, N, wpre ? pl.ext : pl.eb);
-    int *eY = pk<int>(workspace, d, T, N, wpre ? pl.eyt : pl.ec), *eE = d.mode == kGru ? pk<int>(workspace, d, T, N, pl.ed) : eDX;
-    if (wpre) KCTC_HIP_CHECK(hipStreamWaitEvent(s, pre->wev, 0));
-    unsigned *cm = pk<unsigned>(workspace, d, T, N, pl.cm);
-    // two streams (s2, the bottom component's tail, where nothing else
-    // overlaps): input^T and output^T are packed and dW runs on s2 while
-    // dGates^T is packed and dR runs on s (separate split slabs, tile
-    // counters and absmax scratch); s then waits for s2
-    const unsigned *cme0 = pick6(d, N, false) ? pk<unsigned>(workspace, d, T, N, pl.cme) : nullptr;
-    // (LSTM: dR's dGates^T is dW's, E == DX; the GRU's E^T pack stays on one stream)
-    const bool two = s2 && x3 && cme0 && d.mode == kLstm && d.layers == 1 && T > 1 && env_int("KCTC_WGRAD_2S", 1);
-    hipStream_t sx = two ? s2 : s;  // stream of the input / output packs and of dW
-    hipEvent_t ev_dx = nullptr, ev_y = nullptr;
-    if (two) {
-      KCTC_HIP_CHECK(hipEventCreateWithFlags(&ev_dx, hipEventDisableTiming));
-      KCTC_HIP_CHECK(hipEventCreateWithFlags(&ev_y, hipEventDisableTiming));
-      join_stream(s2, s);
-    }
-    if (two) {
-      ProfSpan ps(s, "x3_pack_w");
-      x3p_pack_cols(s, DX, ldg, (int)TN, (int)(dirs * G4), 0, DXt, eDX, cme0, 0.f);
-      KCTC_HIP_CHECK(hipEventRecord(ev_dx, s));
-      const bool xb = l == 0 && in_bound > 0.f;
-      // absmax scratch of its own: the GRU-only E^T exponent array (free for an LSTM)
-      unsigned *cmx = reinterpret_cast<unsigned *>(pk<int>(workspace, d, T, N, pl.ed));
-      if (!wpre) {
-        if (!xb) absmax_f32(s2, in, Din, (int)TN, Din, nullptr, cmx);
-        x3p_pack_cols(s2, in, Din, (int)TN, Din, 0, Xt, eX, cmx, xb ? in_bound : 0.f);
-        for (int dir = 0; dir < dirs; dir++)
-          x3p_pack_cols(s2, out + (long)dir * H, ldy, (int)TN, H, dir == 0 ? N : -N, Yt + (long)dir * H * KBt * 64,
-                        eY + dir * H, nullptr, 1.f);
-      }
-      KCTC_HIP_CHECK(hipEventRecord(ev_y, s2));
-      KCTC_HIP_CHECK(hipStreamWaitEvent(s2, ev_dx, 0));
-      KCTC_HIP_CHECK(hipStreamWaitEvent(s, ev_y, 0));
-    } else if (x3) {
-      // the transposes, packed over the frames: dGates^T (per-gate exponents),
-      // input^T (per-dim), and for dR the output shifted by one step per direction
-      ProfSpan ps(s, "x3_pack_w");
-      // beside a pinned recurrence: off its XCDs (x3p_pack_cols avoid)
-      const unsigned *av = beside ? rnn_pinned_xcds() : nullptr;
-      const int nx = std::max(1, rnn_usable_cus() / kCusPerXcd);
-      // their item counters: flag words 1010..1014 (this component's
-      // recurrences, which use the flag words, are done)
-      int *pc = reinterpret_cast<int *>(fl + 1010);
-      if (av) KCTC_HIP_CHECK(hipMemsetAsync(pc, 0, sizeof(int) * 5, s));
-      // the v6 backward recurrence leaves the dGates column maxima behind
-      const unsigned *cme = cme0;
-      if (!cme) absmax_f32(s, DX, ldg, (int)TN, (int)(dirs * G4), nullptr, cm);
-      x3p_pack_cols(s, DX, ldg, (int)TN, (int)(dirs * G4), 0, DXt, eDX, cme ? cme : cm, 0.f, 1, 0, 0, 0, 0, av, nx,
-                    pc);
-      if (d.mode == kGru) {
-        if (!cme) absmax_f32(s, E, ldg, (int)TN, (int)(dirs * G4), nullptr, cm);
-        x3p_pack_cols(s, E, ldg, (int)TN, (int)(dirs * G4), 0, Et, eE, cme ? cme + dirs * G4 : cm, 0.f, 1, 0, 0, 0,
-                      0, av, nx, pc + 1);
-      }
-      const bool xb = (l > 0 && bounded_out(d)) || (l == 0 && in_bound > 0.f);
-      if (!xb && !wpre) absmax_f32(s, in, Din, (int)TN, Din, nullptr, cm);
-      if (!wpre)
-        x3p_pack_cols(s, in, Din, (int)TN, Din, 0, Xt, eX, cm, xb ? (l > 0 ? 1.f : in_bound) : 0.f, 1, 0, 0, 0, 0,
-                      av, nx, pc + 2);
-      if (T > 1 && !wpre) {
-        if (!bounded_out(d)) absmax_f32(s, out, ldy, (int)TN, (int)ldy, nullptr, cm);
-        for (int dir = 0; dir < dirs; dir++)
-          x3p_pack_cols(s, out + (long)dir * H, ldy, (int)TN, H, dir == 0 ? N : -N, Yt + (long)dir * H * KBt * 64,
-                        eY + dir * H, bounded_out(d) ? nullptr : cm + dir * H, bounded_out(d) ? 1.f : 0.f, 1, 0, 0,
-                        0, 0, av, nx, pc + 3 + dir);
-      }
-    }
-    // beside another component's pinned backward recurrence: dW and dR as
-    // one launch on the CUs it leaves (gemm_x3p_pair; configs[1]: the side
-    // stream fell one GEMM per layer behind, 4 ms of weight GEMMs after the
-    // last recurrence)
-    const bool pair = beside && x3 && !two && T > 1 && x3p_use_256((int)G4, Din) && x3p_use_256((int)G4, H) &&
-                      max_blocks > 0;
-    X3PArgs xw;
-    if (x3) {
-      X3PArgs &x = xw;
-      x.M = (int)G4; x.N = Din; x.KB = KBt;
-      x.A = DXt; x.eA = eDX; x.sA = G4 * KBt * 64; x.seA = G4;
-      x.B = Xt; x.eB = eX;
-      x.C = dwl; x.ldc = Din; x.beta = 1.f;
-      x.batch = dirs; x.sC = pls;
-      x.split_k = x3p_pick_split((int)G4, Din, KBt, dirs);
-      // concurrent with dR: its own split slab past dR's (none when dR is not
-      // split: drec_split_floats reserves a dR slab only for a split > 1)
-      const long sR = x3p_pick_split((int)G4, H, KBt, dirs);
-      x.ws = (two || pair) && sR > 1 ? ws + al64(sR * dirs * G4 * H) : ws;
-      x.max_blocks = g.max_blocks; x.tile_counter = g.tile_counter;
-      if (pair) {
-        x.max_blocks = 192;
-        x.avoid_word = rnn_pinned_xcds();
-        x.avoid_xcds = std::max(1, rnn_usable_cus() / kCusPerXcd);
-      } else {
-        ProfSpan ps(sx, "gemm_bwd_w");
-        gemm_x3p(sx, x);
-      }
-    } else {
-      ProfSpan ps(s, "gemm_bwd_w");
-      gemm_f32(s, g);
-    }
-    // dR_dir += E_dir(shifted)^T h_prev:  fwd pairs rows t>=1 with y rows t-1,
-    // bwd pairs rows t<=T-2 with y rows t+1 (column half H..2H-1)
-    if (T > 1) {
-      GemmArgs r;
-      r.transA = true; r.transB = false;
-      r.M = G4; r.N = H; r.K = (int)((long)(T - 1) * N);
-      r.A = E + (long)N * ldg; r.lda = ldg;
-      r.B = out; r.ldb = ldy;
-      r.C = dwl + (d.lin_offset(l * dirs, NW, false) - pl0); r.ldc = H; r.beta = 1.f;
-      r.batch = dirs;
-      r.strideA = (long)G4 - (long)N * ldg;        // dir 1: E + G4 (rows 0..T-2)
-      r.strideB = (long)N * ldy + H;               // dir 1: y rows 1..T-1, cols H..
-      r.strideC = pls;
-      r.split_k = gemm_pick_split(r.M, r.N, r.K, dirs);
-      r.ws = ws;
-      r.max_blocks = max_blocks;
-      if (max_blocks > 0) r.tile_counter = reinterpret_cast<int *>(fl + 1009);
-      ProfSpan ps(s, "gemm_bwd_r");
-      if (x3) {
-        // all frames: the shifted-out ones are zero in the packed output
-        X3PArgs x;
-        x.M = (int)G4; x.N = H; x.KB = KBt;
-        x.A = Et; x.eA = eE; x.sA = G4 * KBt * 64; x.seA = G4;
-        x.B = Yt; x.eB = eY; x.sB = (long)H * KBt * 64; x.seB = H;
-        x.C = r.C; x.ldc = H; x.beta = 1.f;
-        x.batch = dirs; x.sC = pls;
-        x.split_k = x3p_pick_split((int)G4, H, KBt, dirs); x.ws = ws;
-        x.max_blocks = max_blocks; x.tile_counter = r.tile_counter;
-        if (pair) gemm_x3p_pair(s, xw, x);  // xw's tile counter, block count and avoid word
-        else gemm_x3p(s, x);
-      } else {
-        gemm_f32(s, r);
-      }
-    }
-    if (two) {
-      join_stream(s, s2);
-      (void)hipEventDestroy(ev_dx);
-      (void)hipEventDestroy(ev_y);
-    }
-    }  // x3 / fp32 weight GEMMs
-    // biases: dbW += sum dGx, dbR += sum dGh (partials from the recurrence)
-    const long bW = d.lin_offset(l * dirs, 0, true) - pl0;
-    const long bR = d.lin_offset(l * dirs, NW, true) - pl0;
-    // (v6: one partial per row group, [group][dir][2][G], added in group order)
-    const V6Cfg c6b = pick6(d, N, false);
-    const int rg = c6b ? c6b.rg : 1;
-    for (int gi = 0; gi < rg; gi++)
-      for (int dir = 0; dir < dirs; dir++) {
-        const float *part = R0 + lay.bias + ((long)gi * dirs + dir) * 2 * G4;
-        clip_sgd_update(s, dwl + dir * pls + bW, part, G4, 1.f, 0.f);
-        clip_sgd_update(s, dwl + dir * pls + bR, part + G4, G4, 1.f, 0.f);
-      }
+    const WgradLayer g{d, ws, s, T, N, l,
+                       l == 0 ? x : res + lay.per_layer * (l - 1) + lay.out,
+                       (l == d.layers - 1) ? y : R0 + lay.out,
+                       E, d.mode == kGru ? R0 + lay.DX : E,
+                       dw + lw.pl0, lw.pls, lw.roff, max_blocks};
+    if (x3 && d.prec == kPrecBf16) wgrad_bf16(g, R0, lay, in_cols);
+    else if (x3) wgrad_x3(g, plb.ver == 6, in_bound, s2, beside, pre);
+    else wgrad_f32(g);
+    wgrad_bias(plb, d, s, T, N, dw, reserve, l);
   }
   return KRNN_OK;
 }

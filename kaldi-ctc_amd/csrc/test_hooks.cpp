@@ -45,4 +45,16 @@ int kctc_test_rec6_select(int mode, int prec, int H, int dirs, int N, int fwd, i
   }
 }
 
+int kctc_test_rec_plan(int mode, int prec, int H, int dirs, int N, int fwd, long plan[8]) {
+  if (!plan) return 1;
+  try {
+    kctc::RnnDesc d;
+    d.mode = mode; d.prec = prec; d.D = d.H = H; d.dirs = dirs;
+    kctc::rnn_rec_plan(d, N, fwd != 0, plan);
+    return 0;
+  } catch (...) {
+    return 3;
+  }
+}
+
 }  // extern "C"

@@ -101,7 +101,7 @@ def _backward(kctc, gpu, mode, T, N, pinned):
         r.backward_data(b["y"], b["dy"], b["w"], b["dx"], b["ws"], b["res"])
         torch.cuda.synchronize()
         assert r.device_status() == 0
-    # reserve (rnn.hip rnn_reserve_layout), every part a multiple of 64 floats:
+    # reserve (rnn_plan.hip rnn_reserve_layout), every part a multiple of 64 floats:
     # gate activations [T N][dirs nw H], aux [T N][dirs H], E (as the gate
     # activations), GRU: DX (the same), bias partials [N / 8 groups][dirs][2][nw H]
     al = lambda v: (v + 63) // 64 * 64

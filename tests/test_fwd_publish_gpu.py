@@ -86,7 +86,7 @@ def _forward(kctc, gpu, mode, T, N, pinned):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
-    # reserve (rnn.hip rnn_reserve_layout): gate activations [T N][dirs nw H], then aux [T N][dirs H]
+    # reserve (rnn_plan.hip rnn_reserve_layout): gate activations [T N][dirs nw H], then aux [T N][dirs H]
     nw = 4 if mode == 2 else 3
     n_act, n_aux = T * N * r.dirs * nw * H, T * N * r.dirs * H
     assert n_act % 64 == 0

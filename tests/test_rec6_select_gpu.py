@@ -1,4 +1,4 @@
-"""Which v6 recurrence kernel runs (rnn.hip pick6: V6Cfg's U, nth, rg, gs and
+"""Which v6 recurrence kernel runs (rnn_plan.hip pick6: V6Cfg's U, nth, rg, gs and
 variant), through the test hook kctc_test_rec6_select.  Nothing is launched.
 The table is the selection rule as measured on the recipe shapes
 (profiles/parent_rec6_kernel_names.txt: the kernel names a trace of these

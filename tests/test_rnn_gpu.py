@@ -66,6 +66,9 @@ CASES = [
     # H = 1024 (configs[4] width)
     (3, 12, 8, 40, 1024, 1, True),   # one group, U=16
     (3, 10, 32, 40, 1024, 1, True),  # 2 groups, U=32 on 512-thread workgroups
+    # v3 (no U gives a direction whole XCD slots): the smallest shape that selects it, the only v3 case
+    # (profiles/r10_parent_rec_plan.txt: the cases above run v4 and v6 kernels only)
+    (1, 4, 2, 40, 528, 1, True),
 ]
 
 

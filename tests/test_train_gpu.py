@@ -440,7 +440,7 @@ def test_multistep_trajectory_matches_oracle(kctc, gpu, oracle):
 def test_two_nets_interleaved_on_one_device(kctc, gpu):
     """Two trainers on one device, their steps interleaved (A B A B), each
     bit-identical to its own run alone.  The streamed GEMMs and packs beside
-    a recurrence wait on that launch's own residency count (rnn.hip
+    a recurrence wait on that launch's own residency count (rec_gate.hip
     beside_recurrence), so one net's launches never hold up the other's side
     streams (the round-5 gate waited on a device-wide registration count
     that every net's backward raised)."""

@@ -1,4 +1,4 @@
-"""XCD-pinned recurrences (rnn.hip xcd_mask).
+"""XCD-pinned recurrences (rnn_plan.hip xcd_mask).
 
 At H = 512 (32 workgroups of 16 units per direction) and N <= 16 every
 (row group, direction) of the v6 backward recurrence fits one XCD: the launch
