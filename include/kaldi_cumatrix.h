@@ -24,7 +24,7 @@ int kcm_add_mat_mat(struct ihipStream_t *stream, int transA, int transB, int M, 
 /* The same product on the split-fp16 matrix-core path (fp32-class: every row
  * of op(A) and column of op(B) is scaled by a power of two and carried as an
  * fp16 hi + lo pair, hi*hi + hi*lo + lo*hi accumulated in fp32; both operands
- * are first packed along K, gemm_x3p.hip).  ws: device scratch of at least
+ * are first packed along K, x3p_pack.hip, x3p_gemm.hip).  ws: device scratch of at least
  * kcm_add_mat_mat_x3_workspace(M, N, K) bytes. */
 size_t kcm_add_mat_mat_x3_workspace(int M, int N, int K);
 int kcm_add_mat_mat_x3(struct ihipStream_t *stream, int transA, int transB, int M, int N, int K,

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "elementwise.h"
 #include "gemm.h"
+#include "gemm_x3p.h"
 
 extern "C" {
 

@@ -6,7 +6,7 @@
 //
 // Forward
 //   1. G = x W^T + bW (+ bR): the input projection of all T*N frames of both
-//      directions as one packed split-fp16 GEMM (gemm_x3p.hip) -- or, for the
+//      directions as one packed split-fp16 GEMM (x3p_gemm.hip) -- or, for the
 //      layers above the first, streamed off the previous component's running
 //      recurrence (launch_chain_proj / launch_chain_rows).
 //   2. rnn_fwd_rec6: ONE persistent launch runs the whole time recurrence of
@@ -67,6 +67,7 @@
 #include "common.h"
 #include "elementwise.h"
 #include "gemm.h"
+#include "gemm_x3p.h"
 #include "prof.h"
 #include "rec_common.h"
 #include "rec_gate.h"

@@ -15,7 +15,7 @@ inline int env_int(const char *name, int dflt) {
   const char *v = getenv(name);
   return v ? atoi(v) : dflt;
 }
-// The RNN GEMMs run on the packed split-fp16 matrix-core path (gemm_x3p.hip)
+// The RNN GEMMs run on the packed split-fp16 matrix-core path (x3p_gemm.hip, gemm_x3p.h)
 // unless the contraction is too short to pay for packing.
 inline bool use_x3(int K, int min_k = 128) { return K >= min_k; }
 // |x| <= 1: an LSTM / GRU / TANH layer output
@@ -51,7 +51,7 @@ constexpr size_t kFlagBytes = 4096 + 512 * 128;  // v6: up to 4 row groups x 2 d
 // plus int exponents and float-bit column maxima (G = nW*H).  Byte offsets
 // from the pack area's start.
 struct PackLay {
-  size_t a, b, c, d, ea, eb, ec, ed, cm, part, cnt, part2, cme, fcnt, fpart, wt, ewt, cmw, xt, yt, ext, eyt, pcnt, total;
+  size_t a, b, c, ea, eb, ec, ed, cm, part, cnt, part2, cme, fcnt, fpart, wt, ewt, cmw, xt, yt, ext, eyt, pcnt, total;
 };
 
 // The workspace of (d, T, N): the split-K slabs of the weight-gradient GEMMs,

@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "gemm.h"
+#include "gemm_x3p.h"
 #include "rnn_plan.h"
 
 namespace kctc {
@@ -76,7 +77,6 @@ static PackLay pack_layout(const RnnDesc &d, int T, int N) {
   p.a = o; o = align_up(o + std::max({fw_a, bd_a, bw_a}), 256);
   p.b = o; o = align_up(o + std::max({fw_b, bd_b, bw_b}), 256);
   p.c = o; o = align_up(o + bw_c, 256);
-  p.d = o;  // unused slot kept for symmetry (0 bytes)
   const long ne = std::max({TN * dirs, dirs * G * 2, dirs * Dm}) + 64;
   p.ea = o; o = align_up(o + sizeof(int) * ne, 256);
   p.eb = o; o = align_up(o + sizeof(int) * ne, 256);

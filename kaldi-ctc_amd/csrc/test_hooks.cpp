@@ -5,7 +5,7 @@
 #include <stdexcept>
 
 #include "common.h"
-#include "gemm.h"
+#include "gemm_x3p.h"
 #include "rnn.h"
 
 extern "C" {
@@ -17,6 +17,54 @@ float kcm_bench_gemm_packed(struct ihipStream_t *stream, int M, int N, int K, in
   } catch (...) {
     return -1.f;
   }
+}
+
+int kcm_test_gemm_packed(struct ihipStream_t *stream, int M, int N, int K, int bf16, int split, int dynamic,
+                         int max_blocks, int M2, const float *A, const float *B, float *C, float *C2) {
+  if (!A || !B || !C || M <= 0 || N <= 0 || K <= 0 || split < 1 || M2 < 0 || M2 > M || (M2 > 0 && !C2)) return 1;
+  char *buf = nullptr;
+  int rc = 0;
+  try {
+    const int KB = bf16 ? (K + 63) / 64 : (K + 31) / 32;
+    const size_t ap = (size_t)M * KB * 128, bp = (size_t)N * KB * 128, slab = sizeof(float) * (size_t)split * M * N;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    KCTC_HIP_CHECK(hipMalloc(&buf, up(ap) + up(bp) + 2 * up(slab) + up(sizeof(int) * (size_t)M) +
+                                       up(sizeof(int) * (size_t)N) + up(sizeof(int))));
+    char *o = buf;
+    auto take = [&](size_t b) { char *r = o; o += up(b); return r; };
+    _Float16 *Ap = reinterpret_cast<_Float16 *>(take(ap)), *Bp = reinterpret_cast<_Float16 *>(take(bp));
+    float *ws = reinterpret_cast<float *>(take(slab)), *ws2 = reinterpret_cast<float *>(take(slab));
+    int *eA = reinterpret_cast<int *>(take(sizeof(int) * (size_t)M)), *eB = reinterpret_cast<int *>(take(sizeof(int) * (size_t)N));
+    int *counter = reinterpret_cast<int *>(take(sizeof(int)));
+    if (bf16) {
+      kctc::bf16_pack_rows(stream, A, K, M, K, reinterpret_cast<__bf16 *>(Ap));
+      kctc::bf16_pack_rows(stream, B, K, N, K, reinterpret_cast<__bf16 *>(Bp));
+    } else {
+      kctc::x3p_pack_rows(stream, A, K, M, K, Ap, eA, 0.f);
+      kctc::x3p_pack_rows(stream, B, K, N, K, Bp, eB, 0.f);
+    }
+    kctc::X3PArgs g;
+    g.M = M; g.N = N; g.KB = KB; g.A = Ap; g.B = Bp; g.C = C; g.ldc = N; g.bf16 = bf16 != 0;
+    if (!bf16) { g.eA = eA; g.eB = eB; }
+    if (split > 1) { g.split_k = split; g.ws = ws; }
+    g.max_blocks = max_blocks;
+    if (dynamic || M2 > 0) g.tile_counter = counter;
+    if (M2 > 0) {  // C2 = A[:M2] B^T: the packed rows of A are a prefix
+      kctc::X3PArgs g2 = g;
+      g2.M = M2; g2.C = C2; g2.ws = split > 1 ? ws2 : nullptr;
+      kctc::gemm_x3p_pair(stream, g, g2);
+    } else {
+      kctc::gemm_x3p(stream, g);
+    }
+    KCTC_HIP_CHECK(hipStreamSynchronize(stream));
+    rc = hipGetLastError() == hipSuccess ? 0 : 3;
+  } catch (const std::invalid_argument &) {
+    rc = 1;
+  } catch (...) {
+    rc = 3;
+  }
+  if (buf) (void)hipFree(buf);
+  return rc;
 }
 
 int kcm_test_row_stream(struct ihipStream_t *stream, int M, int N, int K, int forward, int tail_rows,

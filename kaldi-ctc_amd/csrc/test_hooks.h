@@ -16,6 +16,14 @@ struct ihipStream_t;
  * and the RNN GEMMs) on random packed operands, C[M][N] = A[M][K] B[N][K]^T, split-fp16 (bf16 = 0) or bf16
  * operands, split-K slices; -1 on failure. */
 float kcm_bench_gemm_packed(struct ihipStream_t *stream, int M, int N, int K, int bf16, int iters, int split);
+/* The packed GEMM on fp32 device operands A [M][K], B [N][K]: packs both
+ * (split-fp16 rows with their exponents, or bf16 rows) and runs gemm_x3p into
+ * C [M][N] = A B^T.  split > 1: split-K over a slab the hook allocates;
+ * dynamic: tiles dealt from a counter; max_blocks: persistent grid; M2 > 0:
+ * also C2 [M2][N] = A[:M2] B^T, both as one gemm_x3p_pair launch.  1 on
+ * arguments the GEMM refuses, 3 on any other failure. */
+int kcm_test_gemm_packed(struct ihipStream_t *stream, int M, int N, int K, int bf16, int split, int dynamic,
+                         int max_blocks, int M2, const float *A, const float *B, float *C, float *C2);
 /* The streamed direction-split GEMM of the RNN backward (dx) and chained forward (next projection) against a
  * producer that has already finished: C[M][N] = E[:, 0:K] Wt[0]^T +
  * E[:, K:2K] Wt[1]^T (+ bias[c]), E [M][2K], Wt [2][N][K], device pointers;

@@ -21,6 +21,7 @@ SHAPES = [  # (name, M, N, K, bf16, split)
     ("c4_bwd_data", 64000, 2048, 3072, 1, 1),
     ("c4_bwd_w", 3072, 2048, 64000, 1, 4),
     ("c4_bwd_r", 3072, 1024, 64000, 1, 8),
+    ("c4_bwd_w_x3", 3072, 2048, 64000, 0, 8),  # the configs[4] dW shape on split-fp16 operands
     ("sq8192_bf16", 8192, 8192, 8192, 1, 1),
     ("sq8192_x3", 8192, 8192, 8192, 0, 1),
 ]

@@ -1,5 +1,5 @@
-"""The 256-tile streamed direction-split GEMM (gemm_x3p.hip
-x3p_bwd_stream256_kernel: the RNN backward's dx and the chained forward's
+"""The streamed direction-split GEMM (x3p_stream.hip
+x3p_bwd_stream256_kernel, and x3p_bwd_stream_kernel on 128 tiles: the RNN backward's dx and the chained forward's
 next-component projection) in isolation, against a numpy float64 product:
 C = E[:, :K] Wt0^T + E[:, K:] Wt1^T (+ bias), every producer epoch final.
 Both producer orders, with and without the split-K tail slots (whose tiles
@@ -11,10 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("forward", [0, 1])
-@pytest.mark.parametrize("tail", [0, 1, 3])
-@pytest.mark.parametrize("M,N,K", [(256 * 10, 512, 256), (256 * 9 + 16 * 5, 768, 512), (256 * 12, 256, 2048)])
-def test_row_stream_matches_float64(kctc, gpu, forward, tail, M, N, K):
+def run_row_stream(kctc, gpu, forward, tail, M, N, K):
     import torch
     rng = np.random.default_rng(M + N + K + 7 * forward + tail)
     E = rng.standard_normal((M, 2 * K)).astype(np.float32)
@@ -35,4 +32,18 @@ def test_row_stream_matches_float64(kctc, gpu, forward, tail, M, N, K):
     assert np.all(np.isfinite(C))
     scale = np.sqrt(np.mean(ref ** 2))
     err = np.abs(C - ref).max() / scale
+    print(f"row stream M={M} N={N} K={K} forward={forward} tail={tail}: max err / rms = {err:.3e}")
     assert err < 2e-5, err
+
+
+@pytest.mark.parametrize("forward", [0, 1])
+@pytest.mark.parametrize("tail", [0, 1, 3])
+@pytest.mark.parametrize("M,N,K", [(256 * 10, 512, 256), (256 * 9 + 16 * 5, 768, 512), (256 * 12, 256, 2048)])
+def test_row_stream_matches_float64(kctc, gpu, forward, tail, M, N, K):
+    run_row_stream(kctc, gpu, forward, tail, M, N, K)
+
+
+def test_row_stream_128_tile_matches_float64(kctc, gpu):
+    """x3p_bwd_stream_kernel (N < 192: 128 x 128 tiles), a backward producer's
+    order: 20 frames of 16 sequences, three row tiles (the last half full)."""
+    run_row_stream(kctc, gpu, 0, 0, 320, 128, 256)
