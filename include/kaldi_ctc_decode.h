@@ -15,6 +15,13 @@
  *                               pad_input, prob_scale, blank_threshold)
  *   kctc_nnet_compute_prob   <- nnet2-ctc-compute-prob
  *                               (src/ctcbin/nnet2-ctc-compute-prob.cc:27-111)
+ *   kctc_nnet_propagate_seq / kctc_am_nnet_decodable_batch
+ *                            <- the two above for N utterances of different
+ *                               lengths in one batch (an extension)
+ *   kctc_nnet_sum_posteriors <- nnet-ctc-compute-from-egs | matrix-sum-rows |
+ *                               vector-sum (steps/ctc/train.sh:469-510)
+ *   kctc_am_nnet_adjust_priors <- nnet-adjust-priors
+ *   kctc_nnet_insert         <- nnet-insert (src/nnet2/nnet-functions.cc:39-55)
  * Return 0 on success (kctc_last_error() describes a failure).
  */
 #ifndef KALDI_CTC_AMD_KALDI_CTC_DECODE_H_
@@ -62,6 +69,67 @@ int kctc_nnet_propagate(kctcNnet_t nnet, const float *feats_dev, int T_max, int 
  * matrix to out_host (capacity T*A floats), *num_rows = rows kept. */
 int kctc_am_nnet_decodable(kctcNnet_t nnet, const float *feats_dev, int T, float prob_scale,
                            float blank_threshold, float *out_host, int *num_rows);
+
+/* ---- variable-length batches -------------------------------------------------
+ * The reference evaluates one utterance at a time (mini_batch = 1): nothing
+ * masks its sequences, so in a padded batch the reverse direction of a BLSTM
+ * would start on the padding.  Here N utterances of different lengths run as
+ * one batch and each gets exactly the rows it would get alone: the RNN
+ * components take krnnForwardInferenceSeq's path (kaldi_rnn.h), the other
+ * components work row by row.  At most 64 utterances per call.
+ *
+ * kctc_nnet_propagate_seq: kctc_nnet_propagate with host lengths
+ * num_frames[n] in [1, T_max].  Row t*N+n of out_dev (t < num_frames[n]) is
+ * row t of utterance n's own kctc_nnet_propagate (N = 1); the rows
+ * t >= num_frames[n] mean nothing.  Input rows of the padding frames may
+ * hold anything finite.  A DropoutComponent draws one mask for the batch;
+ * evaluate with the dropout components removed, as the recipe does. */
+int kctc_nnet_propagate_seq(kctcNnet_t nnet, const float *feats_dev, int T_max, int N, const int *num_frames,
+                            float *out_dev, long len);
+
+/* kctc_am_nnet_decodable for N utterances at once.  feats_dev
+ * [T_max*N][input_dim]: plain feature rows, time-major (frame t of utterance
+ * n in row t*N+n, t < num_frames[n]; the other rows anything finite).
+ * out_host (capacity sum(num_frames)*A floats) receives the kept rows of
+ * utterance 0, then of utterance 1, ...; rows[n] = rows kept of utterance n
+ * (per utterance: the frames below blank_threshold, or all of its frames if
+ * none is).  A network with frame context goes through kctc_am_nnet_decodable
+ * one utterance at a time (every utterance is padded at its own ends). */
+int kctc_am_nnet_decodable_batch(kctcNnet_t nnet, const float *feats_dev, int T_max, int N, const int *num_frames,
+                                 float prob_scale, float blank_threshold, float *out_host, int *rows);
+
+/* nnet-ctc-compute-from-egs | matrix-sum-rows | vector-sum (steps/ctc/train.sh
+ * :469-510): sum[a] = the network's output column a summed over every output
+ * frame of every example of the archive (binary "ark:").  The examples run in
+ * batches of minibatch_size (1..64) in archive order through the
+ * variable-length forward; of each example the first eg.left_context -
+ * nnet.LeftContext() rows are dropped and the input is not padded
+ * (pad_input = false: NumRows - left - right output frames).  The sum runs
+ * over whatever the network outputs (posteriors when it ends in a
+ * SoftmaxComponent), in fp64 on the device in a fixed order.  sum: A =
+ * output_dim doubles (host); *frames = output frames summed; *num_egs =
+ * examples read. */
+int kctc_nnet_sum_posteriors(kctcNnet_t nnet, const char *rspecifier, int minibatch_size, double *sum, int A,
+                             long *frames, long *num_egs);
+
+/* nnet-adjust-priors (src/nnet2bin/nnet-adjust-priors.cc:126-140).
+ * google_prior_const != 0: priors = 1 with priors[0] = the constant (left
+ * un-normalised, as the reference does; posterior_sum is not read).
+ * Otherwise priors = posterior_sum / sum(posterior_sum), which must be > 0
+ * (divided in fp64, stored as float).  No floor is applied: the reference
+ * registers --prior-floor and never uses it. */
+int kctc_am_nnet_adjust_priors(kctcNnet_t nnet, const double *posterior_sum, int A, float google_prior_const);
+
+/* nnet-insert --randomize-next-component=false (InsertComponents,
+ * src/nnet2/nnet-functions.cc:39-55): the components built from the config
+ * lines (one per line, initialised from `seed`) are inserted before component
+ * insert_at, 0 <= insert_at <= kctc_nnet_num_components (= appended: the
+ * Softmax of train.sh:472-478; in the middle: the BLSTM that train.sh:357-384
+ * adds every add_layers_period iterations).  The existing components keep
+ * their parameters.  Dimensions must chain with both neighbours and a
+ * component with frame context must stay first (as kctc_nnet_set_component);
+ * on an error nothing changes.  No minibatch may be in flight. */
+int kctc_nnet_insert(kctcNnet_t nnet, int insert_at, const char *config, unsigned long long seed);
 
 /* nnet2-ctc-compute-prob over an egs archive (binary "ark:"): examples in
  * batches of 10 in archive order, every example used (no training skip

@@ -14,6 +14,8 @@
  *   krnnForwardTraining         <- cudnn::RecurrentForwardTraining (:34-53,
  *                                  nnet-cudnn-component.cc:545-554)
  *   krnnForwardInference        <- cudnn::RecurrentForwardInference (:15-32, :534-543)
+ *   krnnForwardInferenceSeq     (no counterpart: ForwardInference over sequences of
+ *                                  different lengths, each as if it ran alone)
  *   krnnBackwardData            <- cudnn::RecurrentBackwardData (:55-80, :576-588)
  *   krnnBackwardWeights         <- cudnn::RecurrentBackwardWeights (:83-97, :594-599)
  *
@@ -86,6 +88,26 @@ int krnnForwardTraining(krnnDescriptor_t desc, struct ihipStream_t *stream, int 
 int krnnForwardInference(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length,
                          int minibatch, const float *x, const float *w, float *y,
                          void *workspace, size_t workspace_bytes);
+/* Length-aware inference (an extension; cuDNN 5.1 has no sequence lengths and
+ * the reference therefore evaluates with mini_batch = 1): `minibatch`
+ * sequences of lengths seq_lengths[n] in [1, seq_length] run as one batch,
+ * each with exactly the result it would get alone with hx = cx = 0:
+ *   y[t][n][:] = output of the layer run on x[0:len[n]][n] alone   (t <  len[n])
+ *   y[t][n][:] = 0                                                (t >= len[n])
+ * Rows t >= len[n] of x may hold anything finite; they do not matter.
+ * seq_lengths is a HOST array, consumed before the call returns (it travels
+ * as a kernel argument); the call is ordered on `stream` and does not
+ * synchronise the host.  A length outside [1, seq_length] (or minibatch > 64)
+ * returns KRNN_STATUS_BAD_PARAM / NOT_SUPPORTED and enqueues nothing.  With
+ * num_layers > 1 every stacked layer is aligned on its own.  workspace:
+ * krnnGetInferenceSeqWorkspaceSize bytes (the inference workspace plus one
+ * masked copy of x and one un-shifted copy of a layer's gates and output).
+ * Every mode, recurrence version and precision of krnnForwardInference works:
+ * the recurrences are the same launches. */
+size_t krnnGetInferenceSeqWorkspaceSize(krnnDescriptor_t desc, int seq_length, int minibatch);
+int krnnForwardInferenceSeq(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length,
+                            int minibatch, const int *seq_lengths, const float *x, const float *w,
+                            float *y, void *workspace, size_t workspace_bytes);
 int krnnBackwardData(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length,
                      int minibatch, const float *y, const float *dy, const float *w, float *dx,
                      void *workspace, size_t workspace_bytes, void *reserve,

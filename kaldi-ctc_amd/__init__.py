@@ -236,6 +236,21 @@ class Rnn:
                                                _ptr(y), _ptr(workspace), workspace.numel()),
                     "krnnForwardInference")
 
+    def seq_workspace_size(self, T, N):
+        return lib().krnnGetInferenceSeqWorkspaceSize(self.h, T, N)
+
+    def forward_inference_seq(self, x, seq_lengths, w, y, workspace, stream=None):
+        """krnnForwardInferenceSeq: x [T, N, D] holds N sequences of (host)
+        lengths seq_lengths[n] in [1, T]; y[:len_n, n] is what sequence n gets
+        alone, y[len_n:, n] is 0.  workspace: seq_workspace_size(T, N) bytes."""
+        T, N = x.shape[0], x.shape[1]
+        lens = np.ascontiguousarray(seq_lengths, dtype=np.int32)
+        if lens.shape != (N,):
+            raise RnnError(f"seq_lengths has shape {lens.shape}, expected ({N},)")
+        _krnn_check(lib().krnnForwardInferenceSeq(self.h, _stream_handle(stream), T, N, lens.ctypes.data, _ptr(x),
+                                                  _ptr(w), _ptr(y), _ptr(workspace), workspace.numel()),
+                    "krnnForwardInferenceSeq")
+
     def backward_data(self, y, dy, w, dx, workspace, reserve, stream=None):
         T, N = y.shape[0], y.shape[1]
         _krnn_check(lib().krnnBackwardData(self.h, _stream_handle(stream), T, N, _ptr(y), _ptr(dy),
@@ -623,7 +638,7 @@ class Nnet:
         of feats [T*N*num_splice, D] (FormatNnetInput layout)."""
         import torch
         self._check_feats(feats, T, N)
-        A = int(self.info(self.num_components - 1).split("output-dim=")[1].split(",")[0])
+        A = self.output_dim
         if out is None:
             out = torch.empty((T * N, A), dtype=torch.float32, device=feats.device)
         _tcheck(lib().kctc_nnet_propagate(self.h, _ptr(feats), T, N, _ptr(out), out.numel()), "propagate")
@@ -634,12 +649,96 @@ class Nnet:
         for the network's context as pad_input = true) -> np [kept, A]."""
         if feats.dim() != 2 or feats.shape[0] != T or not feats.is_contiguous():
             raise KctcError(f"feats must be a contiguous [T={T}, input_dim] tensor, got {tuple(feats.shape)}")
-        A = int(self.info(self.num_components - 1).split("output-dim=")[1].split(",")[0])
+        A = self.output_dim
         out = np.empty((T, A), np.float32)
         k = ctypes.c_int()
         _tcheck(lib().kctc_am_nnet_decodable(self.h, _ptr(feats), T, prob_scale, blank_threshold, out.ctypes.data,
                                              ctypes.byref(k)), "am_nnet_decodable")
         return out[:k.value].copy()
+
+    @property
+    def output_dim(self):
+        return int(self.info(self.num_components - 1).split("output-dim=")[1].split(",")[0])
+
+    @staticmethod
+    def _pad_batch(group):
+        """[T_n, D] CUDA tensors -> (time-major [T_max*N, D] tensor, T_max, lengths)."""
+        import torch
+        for f in group:
+            if f.dim() != 2 or f.shape[0] < 1 or f.shape[1] != group[0].shape[1]:
+                raise KctcError(f"every utterance must be a [T >= 1, input_dim] tensor, got {tuple(f.shape)}")
+        nf = np.array([f.shape[0] for f in group], np.int32)
+        padded = torch.nn.utils.rnn.pad_sequence(list(group))  # [T_max, N, D]
+        return padded.reshape(-1, padded.shape[2]).contiguous(), int(nf.max()), nf
+
+    def propagate_batch(self, feats_list, batch_size=16):
+        """NnetComputation of utterances of different lengths, batch_size (<= 64)
+        at a time as one variable-length batch (kctc_nnet_propagate_seq): a list,
+        in input order, of [T_n, output_dim] CUDA tensors, each what
+        propagate(feats, T_n, 1) gives for that utterance alone.  For networks
+        without frame context (their input layout is that of propagate)."""
+        import torch
+        if self.context != (0, 0):
+            raise KctcError("propagate_batch takes plain feature rows: the network must have no frame context")
+        A, outs = self.output_dim, []
+        for g0 in range(0, len(feats_list), batch_size):
+            group = feats_list[g0:g0 + batch_size]
+            feats, T, nf = self._pad_batch(group)
+            N = len(group)
+            out = torch.empty((T * N, A), dtype=torch.float32, device=feats.device)
+            _tcheck(lib().kctc_nnet_propagate_seq(self.h, _ptr(feats), T, N, nf.ctypes.data, _ptr(out), out.numel()),
+                    "propagate_seq")
+            out = out.reshape(T, N, A)
+            outs += [out[:nf[n], n].contiguous() for n in range(N)]
+        return outs
+
+    def decodable_batch(self, feats_list, prob_scale=1.0, blank_threshold=1.0, batch_size=16):
+        """decodable() of any number of utterances ([T_n, D] CUDA tensors, plain
+        rows), run batch_size (<= 64) at a time as variable-length batches
+        (kctc_am_nnet_decodable_batch) -> list of np [kept_n, A] in input order."""
+        A, outs = self.output_dim, []
+        for g0 in range(0, len(feats_list), batch_size):
+            group = feats_list[g0:g0 + batch_size]
+            feats, T, nf = self._pad_batch(group)
+            N = len(group)
+            out = np.empty((int(nf.sum()), A), np.float32)
+            rows = np.zeros(N, np.int32)
+            _tcheck(lib().kctc_am_nnet_decodable_batch(self.h, _ptr(feats), T, N, nf.ctypes.data, prob_scale,
+                                                       blank_threshold, out.ctypes.data, rows.ctypes.data),
+                    "am_nnet_decodable_batch")
+            ends = np.cumsum(rows)
+            outs += [out[e - r:e].copy() for e, r in zip(ends, rows)]
+        return outs
+
+    def sum_posteriors(self, rspecifier, minibatch_size=16):
+        """nnet-ctc-compute-from-egs | matrix-sum-rows | vector-sum over an egs
+        archive -> (sum [output_dim] float64, frames, num_egs)."""
+        A = self.output_dim
+        s = np.zeros(A, np.float64)
+        fr, ne = ctypes.c_long(), ctypes.c_long()
+        _tcheck(lib().kctc_nnet_sum_posteriors(self.h, str(rspecifier).encode(), minibatch_size, s.ctypes.data, A,
+                                               ctypes.byref(fr), ctypes.byref(ne)), "sum_posteriors")
+        return s, fr.value, ne.value
+
+    def adjust_priors(self, posterior_sum=None, google_prior_const=0.0):
+        """nnet-adjust-priors: priors = posterior_sum / its total, or (with
+        google_prior_const) all ones with priors[0] = the constant."""
+        A = self.output_dim
+        if posterior_sum is None:
+            if not google_prior_const:
+                raise KctcError("adjust_priors needs a posterior sum or google_prior_const")
+            s = np.zeros(A, np.float64)
+        else:
+            s = np.ascontiguousarray(posterior_sum, dtype=np.float64)
+            if s.shape != (A,):
+                raise KctcError(f"posterior sum has shape {s.shape}, expected ({A},)")
+        _tcheck(lib().kctc_am_nnet_adjust_priors(self.h, s.ctypes.data, A, float(google_prior_const)),
+                "adjust_priors")
+
+    def insert(self, insert_at, config, seed=0):
+        """nnet-insert (--randomize-next-component=false): the components of
+        the config lines go before component insert_at (num_components: appended)."""
+        _tcheck(lib().kctc_nnet_insert(self.h, int(insert_at), config.encode(), seed), "nnet_insert")
 
     def compute_prob(self, rspecifier):
         """nnet2-ctc-compute-prob -> dict(num_examples, tot_like, tot_accuracy, tot_weight)."""

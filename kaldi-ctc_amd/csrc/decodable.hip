@@ -11,11 +11,13 @@
 //   log_probs -= log(priors)   (when the AmNnet has priors)  (:73-79)
 //   log_probs *= prob_scale                            (:81-82)
 //
-// Kernels: k_softmax_rows (one wave per row), k_blank_scan (one workgroup:
-// ordered compaction of the kept frames, the CopyRows of :63-65), and
-// k_decodable_rows (one wave per kept row: gather, floor, log, prior, scale).
+// Kernels: k_softmax_rows (one wave per row); the blank scan (one workgroup
+// per utterance: ordered compaction of the kept frames, the CopyRows of
+// :63-65) and the row kernel (one wave per kept row: gather, floor, log,
+// prior, scale) are seq_align.hip's, which take a batch of utterances.
 #include "common.h"
 #include "decodable.h"
+#include "seq_align.h"
 
 namespace kctc {
 namespace {
@@ -35,61 +37,6 @@ __global__ __launch_bounds__(256) void k_softmax_rows(const float *__restrict__ 
   const float inv = 1.f / s;
   float *y = out + row * cols;
   for (int j = lane; j < cols; j += 64) y[j] = fmaxf(expf(x[j] - m) * inv, 1.0e-20f);
-}
-
-// dst[t] = index of frame t among the kept frames (or -1); *kept = count.
-// One workgroup scans the T flags in chunks of 1024 in frame order.
-__global__ __launch_bounds__(1024) void k_blank_scan(const float *__restrict__ probs, int T, int A,
-                                                     float blank_threshold, int *__restrict__ dst,
-                                                     int *__restrict__ kept) {
-  __shared__ int wsum[16];
-  __shared__ int base;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const bool skip = blank_threshold < 1.0f;
-  if (tid == 0) base = 0;
-  __syncthreads();
-  for (int c0 = 0; c0 < T; c0 += 1024) {
-    const int t = c0 + tid;
-    const int k = (t < T) && (!skip || probs[(long)t * A] < blank_threshold) ? 1 : 0;
-    // inclusive scan within the wave, then across the 16 waves
-    int v = k;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int u = __shfl_up(v, o, 64);
-      if (lane >= o) v += u;
-    }
-    if (lane == 63) wsum[w] = v;
-    __syncthreads();
-    int off = base;
-    for (int i = 0; i < w; i++) off += wsum[i];
-    if (t < T) dst[t] = k ? off + v - 1 : -1;
-    __syncthreads();
-    if (tid == 1023) base = off + v;
-    __syncthreads();
-  }
-  // "No Frame will be keeped ..., don't skip blank" (:59-61)
-  const bool none = skip && base == 0;
-  if (none)
-    for (int t = tid; t < T; t += 1024) dst[t] = t;
-  if (tid == 0) *kept = none ? T : base;
-}
-
-__global__ __launch_bounds__(256) void k_decodable_rows(const float *__restrict__ probs, int T, int A,
-                                                        const int *__restrict__ dst,
-                                                        const float *__restrict__ priors, float prob_scale,
-                                                        float floor_v, float *__restrict__ out) {
-  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (t >= T) return;
-  const int r = dst[t];
-  if (r < 0) return;
-  const float *p = probs + (long)t * A;
-  float *o = out + (long)r * A;
-  for (int j = lane; j < A; j += 64) {
-    float v = logf(fmaxf(p[j], floor_v));          // ApplyFloor, ApplyLog
-    if (priors) v += -1.0f * logf(priors[j]);      // AddVecToRows(-1.0, log priors)
-    o[j] = v * prob_scale;                         // Scale(prob_scale)
-  }
 }
 
 // DiffSoftmaxPerRow (SoftmaxComponent::Backprop, nnet-component.cc:948-976):
@@ -124,10 +71,9 @@ size_t ctc_decodable_scratch_bytes(int T) { return sizeof(int) * ((size_t)T + 64
 void ctc_decodable(hipStream_t s, const float *probs, int T, int A, const float *priors, float prob_scale,
                    float blank_threshold, float floor_v, float *out, void *scratch, int *kept_dev) {
   if (T <= 0 || A <= 0) return;
-  int *dst = static_cast<int *>(scratch);
-  hipLaunchKernelGGL(k_blank_scan, dim3(1), dim3(1024), 0, s, probs, T, A, blank_threshold, dst, kept_dev);
-  hipLaunchKernelGGL(k_decodable_rows, dim3(ceil_div(T, 4)), dim3(256), 0, s, probs, T, A, dst, priors, prob_scale,
-                     floor_v, out);
+  SeqLens lens{};  // a batch of one utterance (seq_align.hip)
+  lens.len[0] = T;
+  seq_decodable(s, probs, T, 1, A, lens, priors, prob_scale, blank_threshold, floor_v, out, scratch, kept_dev);
 }
 
 }  // namespace kctc

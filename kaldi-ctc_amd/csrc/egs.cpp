@@ -370,7 +370,8 @@ Minibatch::~Minibatch() {
   }
 }
 
-std::unique_ptr<Minibatch> pack_minibatch(std::vector<Example> &egs, int nnet_left, int nnet_right) {
+std::unique_ptr<Minibatch> pack_minibatch(std::vector<Example> &egs, int nnet_left, int nnet_right,
+                                          bool per_example_context) {
   if (egs.empty()) return nullptr;
   auto mb = std::make_unique<Minibatch>();
   const int num_splice = 1 + nnet_left + nnet_right;
@@ -391,7 +392,10 @@ std::unique_ptr<Minibatch> pack_minibatch(std::vector<Example> &egs, int nnet_le
     const Example &e = egs[n];
     if (e.NumCols() != mb->feat_dim || (int)e.spk_info.size() != mb->spk_dim)
       throw std::invalid_argument("FormatNnetInput: examples of different dimensions in one minibatch");
-    const int frames = e.NumFrames() - num_splice - ignore + 1;
+    // (nnet2-ctc-compute-from-egs.cc:80: every example's own start offset)
+    const int ignore_n = per_example_context ? e.left_context - nnet_left : ignore;
+    if (ignore_n < 0) throw std::invalid_argument("FormatNnetInput: left_context < nnet left context");
+    const int frames = e.NumFrames() - num_splice - ignore_n + 1;
     if (frames < 0) throw std::invalid_argument("FormatNnetInput: example shorter than its left context");
     CmHeader h;
     memcpy(&h, e.cm.data(), sizeof(h));
@@ -402,7 +406,7 @@ std::unique_ptr<Minibatch> pack_minibatch(std::vector<Example> &egs, int nnet_le
     d.cols = h.num_cols;
     d.min_value = h.min_value;
     d.range = h.range;
-    d.first = ignore;
+    d.first = ignore_n;
     d.frames = frames;
     d.off = (int64_t)off;
     off = align_up(off + e.cm.size() - sizeof(CmHeader), 16);

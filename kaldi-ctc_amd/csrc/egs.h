@@ -110,8 +110,10 @@ struct Minibatch {
 
 // FormatNnetInput bookkeeping for a vector of examples (num_splice = 1 +
 // nnet left/right context, ignore_frames = left_context - nnet_left_context).
+// per_example_context: ignore_frames from every example's own left_context
+// (nnet2-ctc-compute-from-egs) instead of the first example's (FormatNnetInput).
 std::unique_ptr<Minibatch> pack_minibatch(std::vector<Example> &egs, int nnet_left_context,
-                                          int nnet_right_context);
+                                          int nnet_right_context, bool per_example_context = false);
 
 // NnetCtcExampleBackgroundReader: a producer thread reads and packs the next
 // minibatch while the caller trains on the current one (one slot, two

@@ -539,6 +539,26 @@ void CuDNNRecurrentComponent::Forward(const CuMatrixBase &in, CuMatrixBase *out,
   if (st) throw std::runtime_error("rnn_forward_training failed: " + std::to_string(st));
 }
 
+void CuDNNRecurrentComponent::PropagateSeq(const CuMatrixBase &in, CuMatrixBase *out, const int *num_frames) const {
+  const int N = mini_batch_ > 0 ? mini_batch_ : 1;
+  const int T = (int)(in.NumRows() / N);
+  if (in.NumCols() != desc_.D || in.NumRows() % N || !num_frames)
+    throw std::invalid_argument("CuDNNRecurrentComponent::PropagateSeq: bad input shape");
+  reserve_.ensure(sizeof(float) * rnn_reserve_layout(desc_, T, N).total);
+  workspace_.ensure(rnn_workspace_bytes(desc_, T, N));
+  seq_buf_.ensure(rnn_seq_buffer_bytes(desc_, T, N));
+  // the reserve no longer holds a training forward, and nothing was streamed
+  seq_length_ = 0;
+  input_projected_ = false;
+  in_tn_[0] = in_tn_[1] = -1;
+  pre_.done = pre_.wdone = false;
+  ProfScope ps("layer_rnn_forward");
+  int st = rnn_forward_inference_seq(desc_, S(), T, N, num_frames, in.Data(), params_.f(), out->Data(), workspace_.p,
+                                     workspace_.bytes, reserve_.p, reserve_.bytes, seq_buf_.p, seq_buf_.bytes,
+                                     DeviceError());
+  if (st) throw std::runtime_error("rnn_forward_inference_seq failed: " + std::to_string(st));
+}
+
 void CuDNNRecurrentComponent::Backprop(const ChunkInfo &, const ChunkInfo &,
                                        const CuMatrixBase &in_value, const CuMatrixBase &out_value,
                                        const CuMatrixBase &out_deriv, Component *to_update_in,
@@ -1413,6 +1433,30 @@ void Nnet::SetComponent(int c, Component *component) {
     if (auto *r = dynamic_cast<CuDNNRecurrentComponent *>(x)) r->ClearPackedInput();
 }
 
+void Nnet::Insert(int c_to_insert, const std::string &config, Rng &rng) {  // nnet-functions.cc:39-55
+  if (c_to_insert < 0 || c_to_insert > NumComponents()) throw std::out_of_range("Nnet::Insert: bad index");
+  Nnet src;
+  src.Init(config, rng);  // throws on an empty or non-chaining config
+  const int ns = src.NumComponents();
+  const bool in_ok = c_to_insert == 0 || components_[c_to_insert - 1]->OutputDim() == src.InputDim();
+  const bool out_ok = c_to_insert == NumComponents() || src.OutputDim() == components_[c_to_insert]->InputDim();
+  if (!in_ok || !out_ok) throw std::invalid_argument("Nnet::Insert: dimensions do not match the neighbours");
+  // a component with frame context must stay first (NnetCtcUpdater::SetupChunks)
+  for (int c = 0; c < ns; c++)
+    if (c_to_insert + c > 0 && src.components_[c]->Context() != std::vector<int>{0})
+      throw std::invalid_argument("Nnet::Insert: a component with context other than {0} must come first");
+  if (c_to_insert == 0 && !components_.empty() && components_[0]->Context() != std::vector<int>{0})
+    throw std::invalid_argument("Nnet::Insert: a component with context other than {0} must come first");
+  components_.insert(components_.begin() + c_to_insert, src.components_.begin(), src.components_.end());
+  src.components_.clear();  // ownership moved
+  if (momentum_ != 0.f) SetMomentum(momentum_);
+  for (Component *x : components_)
+    if (auto *r = dynamic_cast<CuDNNRecurrentComponent *>(x)) {
+      r->ClearPackedInput();
+      r->ClearInputBound();
+    }
+}
+
 void Nnet::ZeroStats() {
   for (auto *c : components_) c->ZeroStats();
 }
@@ -1543,6 +1587,45 @@ const CuMatrixBase &NnetCtcUpdater::Forward(const float *feats, int T_max, int N
   SetupChunks(T_max, N);
   forward_data_[0].SetView(const_cast<float *>(feats), (long)T_max * N * nnet_->NumSplice(), nnet_->InputDim());
   Propagate(T_max, N);
+  unsigned herr = 0;
+  KCTC_HIP_CHECK(hipMemcpyAsync(&herr, err_word_.p, sizeof(unsigned), hipMemcpyDeviceToHost, S()));
+  KCTC_HIP_CHECK(hipStreamSynchronize(S()));
+  if (herr) throw std::runtime_error("recurrence hand-off timed out (device error word set)");
+  return forward_data_[C];
+}
+
+const CuMatrixBase &NnetCtcUpdater::ForwardSeq(const float *feats, int T_max, int N, const int *num_frames) {
+  if (pending_) throw std::logic_error("ForwardSeq with queued minibatches (Finish them first)");
+  if (N <= 0 || T_max <= 0 || !num_frames) throw std::invalid_argument("empty minibatch");
+  for (int n = 0; n < N; n++)
+    if (num_frames[n] < 1 || num_frames[n] > T_max)
+      throw std::invalid_argument("ForwardSeq: num_frames[" + std::to_string(n) + "] = " +
+                                  std::to_string(num_frames[n]) + " outside [1, T_max]");
+  const int C = nnet_->NumComponents();
+  set_minibatch(nnet_, N);
+  err_word_.ensure(256);
+  KCTC_HIP_CHECK(hipMemsetAsync(err_word_.p, 0, sizeof(unsigned), S()));
+  forward_data_.resize(C + 1);
+  SetupChunks(T_max, N);
+  forward_data_[0].SetView(const_cast<float *>(feats), (long)T_max * N * nnet_->NumSplice(), nnet_->InputDim());
+  for (int c = 0; c < C; c++) {
+    const Component &comp = nnet_->GetComponent(c);
+    const CuMatrixBase &in = forward_data_[c];
+    CuMatrix &out = forward_data_[c + 1];
+    if (comp.IsIdentityForward()) {
+      out.SetView(in.Data(), in.NumRows(), comp.OutputDim());
+      continue;
+    }
+    out.Resize((long)T_max * N, comp.OutputDim());
+    if (const auto *r = dynamic_cast<const CuDNNRecurrentComponent *>(&comp)) {
+      // no streamed hand-over between RNNs here: it reads un-shifted images
+      r->SetErrorWord(static_cast<unsigned *>(err_word_.p));
+      r->ClearPackedInput();
+      r->PropagateSeq(in, &out, num_frames);
+    } else {
+      comp.Propagate(chunk_info_[c], chunk_info_[c + 1], in, &out);
+    }
+  }
   unsigned herr = 0;
   KCTC_HIP_CHECK(hipMemcpyAsync(&herr, err_word_.p, sizeof(unsigned), hipMemcpyDeviceToHost, S()));
   KCTC_HIP_CHECK(hipStreamSynchronize(S()));

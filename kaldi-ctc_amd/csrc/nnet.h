@@ -308,6 +308,10 @@ class CuDNNRecurrentComponent : public UpdatableComponent {
   // following RNN with only identity-forward components in between; `next`
   // then skips that projection in its own Propagate.
   void PropagateChained(const CuMatrixBase &in, CuMatrixBase *out, const CuDNNRecurrentComponent &next) const;
+  // Length-aware forward (rnn.h rnn_forward_inference_seq): the SetMiniBatch
+  // sequences have host lengths num_frames[n]; out's padding rows are 0.  No
+  // chaining, no packed input, no prepacks; leaves no Backprop state.
+  void PropagateSeq(const CuMatrixBase &in, CuMatrixBase *out, const int *num_frames) const;
   // bf16 one-layer bidirectional components write their output also as the
   // packed bf16 GEMM operands (rnn.h rnn_packed_output); the next RNN reads
   // them instead of packing its input (set by the updater from the RNN below,
@@ -331,7 +335,7 @@ class CuDNNRecurrentComponent : public UpdatableComponent {
   int max_seq_length_ = 2000;
   float param_stddev_ = 0.02f, bias_stddev_ = 0.2f, clip_gradient_ = 5.0f;
   DevBuf params_, grad_;
-  mutable DevBuf reserve_, workspace_;
+  mutable DevBuf reserve_, workspace_, seq_buf_;
   mutable int mini_batch_ = 0, seq_length_ = 0;
   mutable bool input_projected_ = false;  // set by the previous component's PropagateChained
   mutable float input_bound_ = 0.f;       // ditto: bound on |input| (0: unknown)
@@ -521,6 +525,12 @@ class Nnet {
   int LastUpdatableComponent() const;  // -1 when none (nnet-nnet.cc)
   // takes ownership; dimensions must still chain (nnet-nnet.cc:659-665)
   void SetComponent(int c, Component *component);
+  // InsertComponents (nnet-functions.cc:39-55): the components built from the
+  // config lines go before index c_to_insert (NumComponents(): appended); the
+  // existing components keep their parameters and statistics.  Dimensions
+  // must chain and a component with frame context must stay first, as in
+  // SetComponent; throws and changes nothing otherwise.
+  void Insert(int c_to_insert, const std::string &config, Rng &rng);
   // Nnet::LeftContext / RightContext (nnet-nnet.cc:52-73): the sums of the
   // components' first (negated) and last context offsets
   int LeftContext() const;
@@ -592,6 +602,13 @@ class NnetCtcUpdater {
   // NnetComputation (src/nnet2/nnet-compute.cc): forward only, N sequences
   // time-major; the output stays valid until the next minibatch
   const CuMatrixBase &Forward(const float *feats, int T_max, int N);
+  // The same for N sequences of different lengths num_frames[n] in
+  // [1, T_max]: row t*N+n (t < num_frames[n]) is what utterance n gets in a
+  // Forward of its own (N = 1).  The RNN components take the length-aware
+  // path (PropagateSeq), the others work row by row as in Forward; the rows
+  // t >= num_frames[n] of the output are those components' image of zero
+  // rows and mean nothing.
+  const CuMatrixBase &ForwardSeq(const float *feats, int T_max, int N, const int *num_frames);
   // best-path ids ([T_max*N], FindRowMaxId) of the last minibatch Finish()ed
   const std::vector<int> &LastBestPath() const { return last_ids_; }
   // per-utterance CTC costs (-log p, warp-ctc `costs`) of that minibatch

@@ -24,6 +24,10 @@ struct kctcNnetImpl {
   // change, and the output / scratch buffers, grown and kept
   kctc::nnet2::DevBuf dec_priors, dec_out, dec_scratch, dec_input;
   std::vector<float> dec_priors_host;
+  // batched decodable / posterior sum (kaldi_ctc_decode.h): one utterance of a
+  // batch gathered for a spliced network, the per-utterance row counts, the
+  // fp64 column sums and their slab partials
+  kctc::nnet2::DevBuf dec_gather, dec_kept, post_sum, post_scratch;
   // nnet2-ctc model file extras: the CtcTransitionModel exactly as read (opaque
   // bytes, in the mode of the file it came from) and AmNnet's priors
   std::string trans_model;

@@ -171,6 +171,22 @@ int rnn_forward_training(const RnnDesc &d, hipStream_t s, int T, int N, const fl
                          const float *w, float *y, void *workspace, size_t ws_bytes,
                          void *reserve, size_t res_bytes, unsigned *err, RnnFwdChain *chain = nullptr,
                          bool input_projected = false, const void *in_rows = nullptr, RnnPrepack *pre = nullptr);
+// Length-aware inference: N sequences of host lengths seq_lengths[n] in
+// [1, T] (read before the call returns; KRNN_BAD_PARAM otherwise) run as one
+// batch, each with the result it would get alone with hx = cx = 0:
+//   y[t,n,:] = the layer's output for x[0:len[n], n] at frame t   (t < len[n])
+//   y[t,n,:] = 0                                                  (t >= len[n])
+// Rows t >= len[n] of x may hold anything.  The recurrences are the training
+// forward's, unchanged: per stacked layer the reverse direction's columns of
+// the projected gates G are shifted right by T - len[n] frames (seq_align.hip)
+// so that it meets frame len[n]-1 with zero state, and its output is shifted
+// back.  None of the streamed hand-overs (RnnFwdChain, in_rows) is used: they
+// read un-shifted images.  workspace / reserve as rnn_forward_training;
+// seq_buffer: rnn_seq_buffer_bytes(d, T, N) more bytes.
+size_t rnn_seq_buffer_bytes(const RnnDesc &d, int T, int N);
+int rnn_forward_inference_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *x,
+                              const float *w, float *y, void *workspace, size_t ws_bytes, void *reserve,
+                              size_t res_bytes, void *seq_buffer, size_t seq_bytes, unsigned *err);
 // bf16 one-layer bidirectional components: the forward recurrence also writes
 // its output as packed bf16 rows [T*N][2H] and columns [2H][kbt64] into the
 // reserve (the GEMM operands the next component's projection / dW and this

@@ -73,6 +73,7 @@
 #include "rec_gate.h"
 #include "rnn.h"
 #include "rnn_plan.h"
+#include "seq_align.h"
 
 namespace kctc {
 
@@ -753,6 +754,79 @@ int rnn_forward_training(const RnnDesc &d, hipStream_t s, int T, int N, const fl
     }
     if (prepack_w) prepack_y_cols(d, ws, out, TN, N, *pre, s);
     tr.dump("fwd", s, pl.grid, p.nwg, T, dirs, pl.ver, p.xpd);
+    in = out;
+  }
+  return KRNN_OK;
+}
+
+// ---------------------------------------------------------------------------
+// host: length-aware inference (rnn.h rnn_forward_inference_seq)
+// ---------------------------------------------------------------------------
+namespace {
+// the seq buffer: the layer-0 input with its padding zeroed, one layer's
+// projected G before the shift, one layer's output before the shift back
+struct SeqBuf {
+  size_t xz = 0, g = 0, y = 0, total = 0;
+  SeqBuf(const RnnDesc &d, int T, int N) {
+    const size_t TN = (size_t)T * N;
+    xz = 0;
+    g = align_up(sizeof(float) * TN * d.D, 256);
+    y = g + (d.dirs == 2 ? align_up(sizeof(float) * TN * d.dirs * d.nw() * d.H, 256) : 0);
+    total = y + align_up(sizeof(float) * TN * d.dirs * d.H, 256);
+  }
+};
+}  // namespace
+
+size_t rnn_seq_buffer_bytes(const RnnDesc &d, int T, int N) { return SeqBuf(d, T, N).total; }
+
+int rnn_forward_inference_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *x,
+                              const float *w, float *y, void *workspace, size_t ws_bytes, void *reserve,
+                              size_t res_bytes, void *seq_buffer, size_t seq_bytes, unsigned *err) {
+  RecScope rec_scope;
+  if (T <= 0 || N <= 0 || N > 16 * kMaxRT || d.H % 16) return KRNN_NOT_SUPPORTED;
+  SeqLens lens;
+  if (!seq_lens(seq_lengths, T, N, &lens)) return KRNN_BAD_PARAM;
+  const RnnReserveLayout lay = rnn_reserve_layout(d, T, N);
+  if (res_bytes < sizeof(float) * (size_t)lay.total) return KRNN_BAD_PARAM;
+  const RnnWs ws(d, T, N, workspace);
+  if (ws_bytes < ws.bytes()) return KRNN_BAD_PARAM;
+  const SeqBuf sb(d, T, N);
+  if (!seq_buffer || seq_bytes < sb.total) return KRNN_BAD_PARAM;
+  const RecPlan pl = plan_rec(d, N, true);
+  if (!pl) return KRNN_NOT_SUPPORTED;
+  const int H = d.H, dirs = d.dirs, NW = d.nw();
+  const long TN = (long)T * N;
+  char *sbase = static_cast<char *>(seq_buffer);
+  float *xz = reinterpret_cast<float *>(sbase + sb.xz), *gs = reinterpret_cast<float *>(sbase + sb.g),
+        *ys = reinterpret_cast<float *>(sbase + sb.y);
+  float *res = static_cast<float *>(reserve);
+  // padding rows of the input may hold anything: zeroed before the projection
+  seq_align(s, x, xz, T, N, d.D, d.D, lens);
+  const float *in = xz;
+  for (int l = 0; l < d.layers; l++) {
+    const bool last = l == d.layers - 1;
+    float *R0 = res + lay.per_layer * l;
+    float *out = last ? y : R0 + lay.out;
+    const LayerW lw = layer_w(d, l);
+    const float *wl = w + lw.pl0;
+    if (pl.ver == 3) KCTC_HIP_CHECK(hipMemsetAsync(ys, 0xFF, sizeof(float) * TN * dirs * H, s));
+    // no streamed hand-over and no packed input rows here: they read
+    // un-shifted images
+    if (dirs == 2) {
+      // the reverse direction's gate columns move right by T - len[n] frames,
+      // so that every sequence ends at row T-1 where that recurrence starts
+      project_input(d, ws, s, TN, l, in, nullptr, wl, lw, gs);
+      seq_align(s, gs, R0 + lay.G, T, N, dirs * NW * H, NW * H, lens);
+    } else {
+      project_input(d, ws, s, TN, l, in, nullptr, wl, lw, R0 + lay.G);
+    }
+    RecParams p = rec_params(d, pl, ws, T, N, wl, lw, R0, lay, ys, err, s);
+    fwd_rec_params(p, d, pl, ws, R0, lay, false, false, s);
+    RecTrace tr;
+    launch_planned(d, pl, true, p, tr, rec_scope, s);
+    tr.dump("fwd", s, pl.grid, p.nwg, T, dirs, pl.ver, p.xpd);
+    // ... and its output moves back; padding rows of both directions become 0
+    seq_unalign(s, ys, out, T, N, dirs * H, H, lens);
     in = out;
   }
   return KRNN_OK;

@@ -126,6 +126,37 @@ int krnnForwardInference(krnnDescriptor_t desc, struct ihipStream_t *stream, int
   }
 }
 
+// [recurrence scratch | reserve] of the length-aware inference workspace, each 256-byte aligned
+static size_t seq_base_bytes(krnnDescriptor_t desc, int T, int N) {
+  return kctc::align_up(kctc::rnn_workspace_bytes(desc->desc, T, N), 256) +
+         kctc::align_up(krnnGetTrainingReserveSize(desc, T, N), 256);
+}
+
+size_t krnnGetInferenceSeqWorkspaceSize(krnnDescriptor_t desc, int seq_length, int minibatch) {
+  if (!desc || seq_length <= 0 || minibatch <= 0) return 0;
+  return seq_base_bytes(desc, seq_length, minibatch) + kctc::rnn_seq_buffer_bytes(desc->desc, seq_length, minibatch);
+}
+
+int krnnForwardInferenceSeq(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length, int minibatch,
+                            const int *seq_lengths, const float *x, const float *w, float *y, void *workspace,
+                            size_t workspace_bytes) {
+  if (!desc || !seq_lengths || !x || !w || !y || !workspace || seq_length <= 0 || minibatch <= 0)
+    return KRNN_STATUS_BAD_PARAM;
+  if (workspace_bytes < krnnGetInferenceSeqWorkspaceSize(desc, seq_length, minibatch))
+    return KRNN_STATUS_BAD_PARAM;
+  // [recurrence scratch | reserve (as krnnForwardInference) | seq buffer]
+  const size_t scratch = kctc::align_up(kctc::rnn_workspace_bytes(desc->desc, seq_length, minibatch), 256);
+  const size_t base = seq_base_bytes(desc, seq_length, minibatch);
+  char *ws = static_cast<char *>(workspace);
+  try {
+    return kctc::rnn_forward_inference_seq(desc->desc, stream, seq_length, minibatch, seq_lengths, x, w, y, ws,
+                                           scratch, ws + scratch, base - scratch, ws + base, workspace_bytes - base,
+                                           desc->dev_err());
+  } catch (...) {
+    return KRNN_STATUS_EXECUTION_FAILED;
+  }
+}
+
 int krnnBackwardData(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length,
                      int minibatch, const float *y, const float *dy, const float *w, float *dx,
                      void *workspace, size_t workspace_bytes, void *reserve,

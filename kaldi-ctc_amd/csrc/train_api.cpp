@@ -21,6 +21,7 @@
 #include "kaldi_io.h"
 #include "nnet.h"
 #include "nnet_handle.h"
+#include "seq_align.h"
 
 using kctc::nnet2::CuDevice;
 
@@ -339,6 +340,26 @@ static kctc::nnet2::UpdatableComponent &ucomp(kctcNnet_t n, int c) {
   auto &x = comp(n, c);
   if (!x.IsUpdatable()) throw std::invalid_argument("component is not updatable");
   return static_cast<kctc::nnet2::UpdatableComponent &>(x);
+}
+
+// the model's priors on the device (nullptr: none), uploaded again only when they change
+static const float *device_priors(kctcNnet_t n, int A) {
+  if (n->priors.empty()) return nullptr;
+  KCTC_REQUIRE((int)n->priors.size() == A, "priors dimension != network output dimension");
+  if (n->dec_priors_host != n->priors) {
+    n->dec_priors.ensure(sizeof(float) * A);
+    KCTC_HIP_CHECK(hipMemcpyAsync(n->dec_priors.p, n->priors.data(), sizeof(float) * A, hipMemcpyHostToDevice,
+                                  n->stream));
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));  // the source is the host vector
+    n->dec_priors_host = n->priors;
+  }
+  return n->dec_priors.f();
+}
+
+// kctc_nnet_profile of the forward-only entry points: their spans are complete
+// after the stream synchronisation (a training step in flight collects its own)
+static void collect_profile(kctcNnet_t n) {
+  if (n->trainer.Pending() == 0 && n->evaluator.Pending() == 0) CuDevice::Instantiate().Collect();
 }
 
 extern "C" {
@@ -956,18 +977,7 @@ int kctc_am_nnet_decodable(kctcNnet_t n, const float *feats_dev, int T, float pr
     const auto &o = n->evaluator.Forward(in, T, 1);
     const int A = o.NumCols();
     auto &out = n->dec_out, &scratch = n->dec_scratch;
-    const float *pd = nullptr;
-    if (!n->priors.empty()) {
-      KCTC_REQUIRE((int)n->priors.size() == A, "priors dimension != network output dimension");
-      if (n->dec_priors_host != n->priors) {
-        n->dec_priors.ensure(sizeof(float) * A);
-        KCTC_HIP_CHECK(hipMemcpyAsync(n->dec_priors.p, n->priors.data(), sizeof(float) * A, hipMemcpyHostToDevice,
-                                      n->stream));
-        KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));  // the source is the host vector
-        n->dec_priors_host = n->priors;
-      }
-      pd = n->dec_priors.f();
-    }
+    const float *pd = device_priors(n, A);
     out.ensure(sizeof(float) * (size_t)T * A);
     scratch.ensure(kctc_ctc_decodable_scratch_bytes(T));
     int kept = 0;
@@ -977,6 +987,155 @@ int kctc_am_nnet_decodable(kctcNnet_t n, const float *feats_dev, int T, float pr
     KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
     KCTC_HIP_CHECK(hipMemcpy(out_host, out.p, sizeof(float) * (size_t)kept * A, hipMemcpyDeviceToHost));
     *num_rows = kept;
+  });
+}
+
+int kctc_nnet_propagate_seq(kctcNnet_t n, const float *feats_dev, int T_max, int N, const int *num_frames,
+                            float *out_dev, long len) {
+  return guarded([&] {
+    KCTC_REQUIRE(n && feats_dev && out_dev && num_frames, "kctc_nnet_propagate_seq: null argument");
+    n->activate();
+    const auto &o = n->evaluator.ForwardSeq(feats_dev, T_max, N, num_frames);
+    KCTC_REQUIRE(len == o.NumRows() * (long)o.NumCols(), "kctc_nnet_propagate_seq: len != T_max*N*output_dim");
+    KCTC_HIP_CHECK(hipMemcpyAsync(out_dev, o.Data(), sizeof(float) * len, hipMemcpyDeviceToDevice, n->stream));
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+    collect_profile(n);
+  });
+}
+
+int kctc_am_nnet_decodable_batch(kctcNnet_t n, const float *feats_dev, int T_max, int N, const int *num_frames,
+                                 float prob_scale, float blank_threshold, float *out_host, int *rows) {
+  return guarded([&] {
+    KCTC_REQUIRE(n && feats_dev && num_frames && out_host && rows && T_max > 0 && N > 0,
+                 "kctc_am_nnet_decodable_batch: bad argument");
+    long total = 0;
+    for (int u = 0; u < N; u++) {
+      KCTC_REQUIRE(num_frames[u] >= 1 && num_frames[u] <= T_max,
+                   "kctc_am_nnet_decodable_batch: num_frames outside [1, T_max]");
+      total += num_frames[u];
+    }
+    n->activate();
+    const int D = n->nnet.InputDim();
+    if (n->nnet.NumSplice() > 1) {
+      // a network with frame context pads every utterance at its own ends
+      // (pad_input = true): one utterance at a time through kctc_am_nnet_decodable
+      long off = 0;
+      for (int u = 0; u < N; u++) {
+        const int T = num_frames[u];
+        n->dec_gather.ensure(sizeof(float) * (size_t)T * D);
+        KCTC_HIP_CHECK(hipMemcpy2DAsync(n->dec_gather.p, sizeof(float) * D, feats_dev + (size_t)u * D,
+                                        sizeof(float) * (size_t)N * D, sizeof(float) * D, T,
+                                        hipMemcpyDeviceToDevice, n->stream));
+        const int A = n->nnet.OutputDim();
+        if (kctc_am_nnet_decodable(n, n->dec_gather.f(), T, prob_scale, blank_threshold, out_host + off * A,
+                                   &rows[u]))
+          throw std::runtime_error(g_err);
+        off += rows[u];
+      }
+      return;
+    }
+    kctc::SeqLens lens;
+    KCTC_REQUIRE(kctc::seq_lens(num_frames, T_max, N, &lens), "kctc_am_nnet_decodable_batch: more than 64 utterances");
+    const auto &o = n->evaluator.ForwardSeq(feats_dev, T_max, N, num_frames);
+    const int A = o.NumCols();
+    const float *pd = device_priors(n, A);
+    n->dec_out.ensure(sizeof(float) * (size_t)total * A);
+    n->dec_scratch.ensure(kctc::seq_decodable_scratch_bytes(T_max, N));
+    n->dec_kept.ensure(sizeof(int) * kctc::kSeqMaxN);
+    int *kept_dev = static_cast<int *>(n->dec_kept.p);
+    kctc::seq_decodable(n->stream, o.Data(), T_max, N, A, lens, pd, prob_scale, blank_threshold, 1.0e-10f,
+                        n->dec_out.f(), n->dec_scratch.p, kept_dev);
+    KCTC_HIP_CHECK(hipMemcpyAsync(rows, kept_dev, sizeof(int) * N, hipMemcpyDeviceToHost, n->stream));
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+    collect_profile(n);
+    long kept = 0;
+    for (int u = 0; u < N; u++) kept += rows[u];
+    KCTC_REQUIRE(kept <= total, "kctc_am_nnet_decodable_batch: kept more rows than frames");
+    KCTC_HIP_CHECK(hipMemcpy(out_host, n->dec_out.p, sizeof(float) * (size_t)kept * A, hipMemcpyDeviceToHost));
+  });
+}
+
+int kctc_nnet_sum_posteriors(kctcNnet_t n, const char *rspecifier, int minibatch_size, double *sum, int A,
+                             long *frames, long *num_egs) {
+  return guarded([&] {
+    KCTC_REQUIRE(n && rspecifier && sum, "kctc_nnet_sum_posteriors: null argument");
+    KCTC_REQUIRE(minibatch_size >= 1 && minibatch_size <= kctc::kSeqMaxN,
+                 "kctc_nnet_sum_posteriors: minibatch_size outside [1, 64]");
+    KCTC_REQUIRE(A == n->nnet.OutputDim(), "kctc_nnet_sum_posteriors: A != network output dimension");
+    n->activate();
+    n->post_sum.ensure(sizeof(double) * A);
+    KCTC_HIP_CHECK(hipMemsetAsync(n->post_sum.p, 0, sizeof(double) * A, n->stream));
+    kctc::egs::ArchiveReader reader(rspecifier);
+    std::vector<kctc::egs::Example> batch;
+    long ne = 0, nf = 0;
+    auto run = [&]() {
+      // every example from its own start offset (eg.left_context - nnet.LeftContext()), pad_input = false
+      std::unique_ptr<kctc::egs::Minibatch> mb =
+          kctc::egs::pack_minibatch(batch, n->nnet.LeftContext(), n->nnet.RightContext(), true);
+      if (mb->InputDim() != n->nnet.InputDim())
+        throw std::invalid_argument("egs input dim " + std::to_string(mb->InputDim()) + " != nnet input dim " +
+                                    std::to_string(n->nnet.InputDim()));
+      kctc::SeqLens lens;
+      if (!kctc::seq_lens(mb->num_frames.data(), mb->T_max, mb->N, &lens))
+        throw std::invalid_argument("an example is shorter than the network's context");
+      n->egs_feats.ensure(sizeof(float) * (size_t)mb->T_max * mb->N * mb->num_splice * mb->InputDim());
+      n->egs_scratch.ensure(kctc::egs::format_scratch_bytes(*mb));
+      kctc::egs::format_on_device(*mb, n->egs_feats.f(), n->egs_scratch.p, n->egs_scratch.bytes, n->stream);
+      const auto &o = n->evaluator.ForwardSeq(n->egs_feats.f(), mb->T_max, mb->N, mb->num_frames.data());
+      n->post_scratch.ensure(kctc::seq_post_sum_scratch_bytes(mb->T_max, mb->N, A));
+      kctc::seq_post_sum(n->stream, o.Data(), mb->T_max, mb->N, A, lens, static_cast<double *>(n->post_sum.p),
+                         n->post_scratch.p);
+      for (int f : mb->num_frames) nf += f;
+      batch.clear();
+    };
+    kctc::egs::Example eg;
+    while (reader.Next(&eg)) {
+      if ((int)batch.size() == minibatch_size) run();
+      batch.push_back(std::move(eg));
+      eg = kctc::egs::Example();
+      ne++;
+    }
+    if (!batch.empty()) run();
+    KCTC_HIP_CHECK(hipMemcpyAsync(sum, n->post_sum.p, sizeof(double) * A, hipMemcpyDeviceToHost, n->stream));
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+    collect_profile(n);
+    if (frames) *frames = nf;
+    if (num_egs) *num_egs = ne;
+  });
+}
+
+int kctc_am_nnet_adjust_priors(kctcNnet_t n, const double *posterior_sum, int A, float google_prior_const) {
+  return guarded([&] {  // nnet-adjust-priors.cc:126-140
+    KCTC_REQUIRE(n, "kctc_am_nnet_adjust_priors: null argument");
+    KCTC_REQUIRE(A == n->nnet.OutputDim(), "kctc_am_nnet_adjust_priors: A != number of pdfs");
+    std::vector<float> p((size_t)A, 1.0f);
+    if (google_prior_const != 0.f) {
+      p[0] = google_prior_const;  // un-normalised, as the reference leaves it
+    } else {
+      KCTC_REQUIRE(posterior_sum, "kctc_am_nnet_adjust_priors: null posterior sum");
+      double tot = 0.0;
+      for (int a = 0; a < A; a++) tot += posterior_sum[a];
+      KCTC_REQUIRE(tot > 0.0, "kctc_am_nnet_adjust_priors: the posterior sum must be positive");
+      for (int a = 0; a < A; a++) p[a] = (float)(posterior_sum[a] / tot);
+    }
+    n->priors = p;
+  });
+}
+
+int kctc_nnet_insert(kctcNnet_t n, int insert_at, const char *config, unsigned long long seed) {
+  return guarded([&] {
+    KCTC_REQUIRE(n && config, "kctc_nnet_insert: null argument");
+    KCTC_REQUIRE(n->trainer.Pending() == 0 && n->evaluator.Pending() == 0,
+                 "kctc_nnet_insert with minibatches in flight");
+    n->activate();
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+    if (n->side) KCTC_HIP_CHECK(hipStreamSynchronize(n->side));
+    kctc::nnet2::Rng rng(seed);
+    n->nnet.Insert(insert_at, config, rng);
+    // what is indexed by component: the two updaters' forward data and chunk info
+    n->trainer.ComponentsChanged();
+    n->evaluator.ComponentsChanged();
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
   });
 }
 
