@@ -50,6 +50,11 @@ namespace {
 #endif
 // stacked backward: partial-dh stores pipelined behind the next tile's MFMAs
 constexpr bool kPipeStk = KCTC_PIPE_STK != 0;
+#ifndef KCTC_STK_HO4
+#define KCTC_STK_HO4 1
+#endif
+// stacked backward: the hand-off loads on half the waves, every lane live
+constexpr bool kStkHo4 = KCTC_STK_HO4 != 0;
 #ifndef KCTC_EARLY_E
 #define KCTC_EARLY_E 1
 #endif
@@ -375,7 +380,15 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   };
   // consumer chunk of this thread: position pos (of the own column tiles'
   // C-fragment chunks) of producers pg, pg + NGRP, ...
-  const int pos = tid % POS, pg = tid / POS;
+  // HO4 (stacked, 32 live chunks a tile): the lower half of the waves load,
+  // half a wave per producer -- lanes 0..31 the 512-B run of producer pg,
+  // lanes 32..63 that of pg + 1 -- the same four producers in the same order
+  // as the live half of wave pg did; the upper half of the waves load nothing
+  constexpr bool HO4 = STK && kStkHo4;
+  static_assert(!HO4 || (POS == 64 && 8 * U <= NTH / 2), "32 live chunks a tile; the element waves load");
+  const bool ho_wave = !HO4 || __builtin_amdgcn_readfirstlane(w) < NWV / 2;
+  // (a wave that does not load: its pg, past the producer groups, is never used)
+  const int pos = HO4 ? tid % (POS / 2) : tid % POS, pg = HO4 ? tid / (POS / 2) : tid / POS;
   const int pln = U >= 16 ? pos : (pos >> 3) * 16 + fr0 + (pos & 7);
   const long coff = (long)grp * xgrp + (long)d * NWG * PSTR + ((long)ct_own * 64 + pln) * LW + (long)pg * PSTR;
   // a C-fragment lane holds rows 4 (lane / 16) .. +3 of the group: quads past N
@@ -437,9 +450,10 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   // consumer's step ks - 1 words, stored after that consumer's loads of step
   // ks - 2 had returned.  Nothing here rests on a wait at the end of a step
   // (STK has none): a consumer's loads of step ks - 2 are retired by its own
-  // poll's vmcnt(0), every wave's, before the step's first barrier, and its
-  // step ks - 1 words follow its second; a wave's stores to one slot, two
-  // steps apart, have the poll between them retiring the older.
+  // poll's vmcnt(0), every loading wave's, before the step's first barrier,
+  // and its step ks - 1 words follow its second; a wave's stores to one slot,
+  // two steps apart, have the poll between them retiring the older (HO4: a
+  // wave that does not load has an explicit vmcnt(0) where the poll was).
   const bool dtag = !BF && p.dtag && local && p.ring == 2;
   // step t's DX rows for a streaming consumer on other XCDs, from the LDS
   // stage: written through (sc1) as whole 16-B chunks, 4 lanes per
@@ -501,6 +515,13 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
 #pragma unroll
           for (int j = 0; j < 4; j++) sm[j] += (float)b[j];
         }
+      } else if (HO4 && !ho_wave) {
+        // no hand-off loads, so no poll whose wait retires this wave's older
+        // stores (partial dh two steps apart into one ring slot; waves 4, 5:
+        // the write-through dGates rows behind the aggregated epoch): the
+        // wait itself, in front of the step's first barrier, where this wave
+        // idles for the loading waves anyway
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       } else {
         u32x4 v[PER];
         // unconditional loads (a dead row quad at an offset past the buffer:
@@ -547,14 +568,17 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
         sm = __builtin_bit_cast(floatx4, v[0]);
 #pragma unroll
         for (int i = 1; i < PER; i++) sm += __builtin_bit_cast(floatx4, v[i]);
+        // (HO4: the element waves are loading waves, and the rotate stays on
+        // their arm, in front of the join with the waves that did not load)
+        if constexpr (HO4) rotate();
       }
-      st4(red + (long)(pg * POS + pos) * 4, sm);
+      if (ho_wave) st4(red + (long)(pg * POS + pos) * 4, sm);
       REC_TRACE(ks, 2);
       REC_TRACE_W(ks, 24);
       // behind the hand-off wait, which retired the last step's prefetch too
       // (on this path: a rotate behind the branches' join waits again, for
       // the loads the compiler must assume on the path without a hand-off)
-      if constexpr (STK) rotate();
+      if constexpr (STK && !HO4) rotate();
       // behind this step's hand-off loads: the write-through copies for the
       // streamed dx GEMM -- the previous step's dGates rows (staged in LDS)
       // and the epoch the last signal drained (step ks - 2's rows).  Issued
@@ -584,7 +608,8 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
     else if (bad_lds) bad = 1;
     // self-tagged: every producer's words of step ks - 1 were stored behind
     // its second barrier of that step, which every wave reached after its
-    // poll -- the hand-off loads' vmcnt(0), in order -- had retired the
+    // poll -- the hand-off loads' vmcnt(0), in order; HO4, waves 4..7: the
+    // explicit vmcnt(0) in its place -- had retired the
     // write-through rows it issued in step ks - 2, those of step ks - 3
     // -> epoch ks (rows of step k out at epoch k + 3; no wait at the end of
     // a step is part of this);
