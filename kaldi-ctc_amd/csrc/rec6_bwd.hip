@@ -19,7 +19,7 @@ namespace {
 //   (4) publishes that partial dh of ALL H units, fp32, in the MFMA C-fragment
 //       layout [producer][col tile][lane][4] (1 KB per 16 x 16 tile).
 // Per WG and step 32 KB are read and 32 KB written (BLSTM-512, N=16) instead of
-// the 128 KB dGates all-gather of v4.
+// the 128 KB dGates all-gather of the generic backward (rec_generic.hip).
 //
 // Split-fp16 products ("fp16x3"): both operands are scaled by powers of two
 // (R slice: one exponent per WG, from its max |R|; dGates: one exponent per
@@ -34,7 +34,7 @@ namespace {
 //
 // R lives in registers for the whole launch (the B fragments of the wave's
 // H/64 column tiles, hi and lo); dGates goes through a 4.5 KB LDS image.
-// Hand-off as v4 (sc1 payload stores, vmcnt(0), barrier, sc1 epoch flag;
+// Hand-off as rec_generic.hip (sc1 payload stores, vmcnt(0), barrier, sc1 epoch flag;
 // sc1 loads) into a per-step image that is never rewritten within a launch.
 // Generalisation (row groups, wide workgroups, bf16): the N sequences are
 // split into RG = ceil(N / 16) groups of 16 rows, each an independent
@@ -45,21 +45,10 @@ namespace {
 // H / (16 NTH / 64) output column tiles).  P = kPrecBf16 multiplies bf16
 // dGates by a bf16 R slice instead of the split-fp16 pair (one MFMA per
 // block, no scaling; partial dh stay fp32).
-#ifndef KCTC_PIPE_STK
-#define KCTC_PIPE_STK 1
-#endif
-// stacked backward: partial-dh stores pipelined behind the next tile's MFMAs
-constexpr bool kPipeStk = KCTC_PIPE_STK != 0;
-#ifndef KCTC_STK_HO4
-#define KCTC_STK_HO4 1
-#endif
-// stacked backward: the hand-off loads on half the waves, every lane live
-constexpr bool kStkHo4 = KCTC_STK_HO4 != 0;
-#ifndef KCTC_EARLY_E
-#define KCTC_EARLY_E 1
-#endif
-// bf16 backward: the previous step's dGates stores under the hand-off loads
-constexpr bool kEarlyE = KCTC_EARLY_E != 0;
+// Stacked backward: the partial-dh stores are pipelined behind the next tile's
+// MFMAs, and the hand-off loads run on half the waves with every lane live
+// (HO4).  bf16 backward: the previous step's dGates stores go under the
+// hand-off loads.
 template <int MODE, int U, int H, int NTH, int P>
 __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   REC_TRACE_INIT;
@@ -384,7 +373,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   // half a wave per producer -- lanes 0..31 the 512-B run of producer pg,
   // lanes 32..63 that of pg + 1 -- the same four producers in the same order
   // as the live half of wave pg did; the upper half of the waves load nothing
-  constexpr bool HO4 = STK && kStkHo4;
+  constexpr bool HO4 = STK;
   static_assert(!HO4 || (POS == 64 && 8 * U <= NTH / 2), "32 live chunks a tile; the element waves load");
   const bool ho_wave = !HO4 || __builtin_amdgcn_readfirstlane(w) < NWV / 2;
   // (a wave that does not load: its pg, past the producer groups, is never used)
@@ -501,7 +490,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
           __builtin_amdgcn_sched_barrier(0);
           coef(k);  // while the hand-off loads are in flight
           __builtin_amdgcn_sched_barrier(0);
-        } else if (kEarlyE) {
+        } else {
           // bf16: the previous step's dGates rows / packed operands (its
           // cell's estg stage, complete since the MFMA phase's barrier) while
           // the hand-off loads are in flight, instead of after them
@@ -592,7 +581,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
     }
     asm volatile("" ::: "memory");
     // behind the hand-off loads: next step's operands, last step's row-major dGates
-    if (t_prev >= 0 && !(kEarlyE && !PRE && bfp && ks > 0)) e_store(t_prev);
+    if (t_prev >= 0 && !(!PRE && bfp && ks > 0)) e_store(t_prev);
     if constexpr (STK) {
       if (k > 1) prefetch(k - 2);
     } else {
@@ -712,7 +701,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
     REC_TRACE(ks, 12);
     __syncthreads();
     REC_TRACE(ks, 3);
-    if (STK && k > 0 && kPipeStk) {
+    if (STK && k > 0) {
       // partial dh of all units for the next step, stacked hi / lo: tile c's
       // four MFMAs, then -- while tile c + 1's run -- its fold, scaling, tag
       // and 16-B store, as one straight-line block per cache policy (the
@@ -764,7 +753,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
       };
       if (local) phase(std::integral_constant<int, 0>{});
       else phase(std::integral_constant<int, 16>{});
-    } else if (BF && k > 0 && kPipeStk && bfp) {
+    } else if (BF && k > 0 && bfp) {
       // bf16 with bf16 partials (configs[4]): the same pipeline -- tile c's KB
       // MFMAs, then its bf16 pack and 8-B store behind tile c + 1's
       const auto ro = rsrc(p.xch + (long)(p.ring ? ks & 1 : ks) * xstep, (unsigned)(xstep * 4));

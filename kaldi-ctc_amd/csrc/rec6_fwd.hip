@@ -20,9 +20,9 @@ __device__ __attribute__((used)) unsigned rec6_fwd_tid() { return threadIdx.x; }
 // update of its (n, unit) elements and publishes h_t as the fp16 hi/lo pair
 // of its units.  The exchange image of a step is A-fragment-major:
 // [dir][kb = k/32][hi|lo][16 rows][32 k] halves (1 KB per fragment), the same
-// 64 KB per step as the fp32 image of v4; a consumer lane loads 16 B of hi
+// 64 KB per step as the fp32 image of rec_generic.hip; a consumer lane loads 16 B of hi
 // and 16 B of lo per 32-k block.  The R slice lives in registers (B
-// fragments) for the whole launch.  Hand-off as v4 (sc1 stores, vmcnt(0),
+// fragments) for the whole launch.  Hand-off as there (sc1 stores, vmcnt(0),
 // barrier, sc1 epoch flag; sc1 loads).
 // Generalised like rnn_bwd_rec6: row groups of 16 sequences (block b ->
 // direction b % dirs, workgroup (b / dirs) % NWG, group b / (dirs NWG); each

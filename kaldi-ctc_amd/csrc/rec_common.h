@@ -1,5 +1,5 @@
-// rec_common.h -- what the recurrence kernels (rec_generic.hip: v3 / v4,
-// rec6_fwd.hip, rec6_bwd.hip: v6) and their host (rnn.hip, rnn_plan.hip,
+// rec_common.h -- what the recurrence kernels (rec_generic.hip: the generic
+// pair, rec6_fwd.hip, rec6_bwd.hip: v6) and their host (rnn.hip, rnn_plan.hip,
 // rec_gate.hip) share: RecParams,
 // the hand-off helpers, trace stamps, the named flag words; V6Cfg and the
 // kernel lookups.  The unnamed namespace's contents are per translation unit.
@@ -21,11 +21,11 @@ struct V6Cfg {
   explicit operator bool() const { return U > 0; }
 };
 // The __global__ function of a recurrence (to launch, or to ask for its
-// attributes); std::logic_error for a shape that is not compiled.  v3 / v4:
-// ver, rt = 16-row tiles of the batch.
+// attributes); std::logic_error for a shape that is not compiled.  Generic:
+// rt = 16-row tiles of the batch.
 const void *rec6_fwd_kernel(int mode, int prec, int H, const V6Cfg &c);
 const void *rec6_bwd_kernel(int mode, int prec, int H, const V6Cfg &c);
-const void *rec_generic_kernel(bool fwd, int ver, int mode, int rt);
+const void *rec_generic_kernel(bool fwd, int mode, int rt);
 inline const void *rec6_kernel(bool fwd, int mode, int prec, int H, const V6Cfg &c) {
   return fwd ? rec6_fwd_kernel(mode, prec, H, c) : rec6_bwd_kernel(mode, prec, H, c);
 }
@@ -33,17 +33,12 @@ inline const void *rec6_kernel(bool fwd, int mode, int prec, int H, const V6Cfg 
 namespace {
 
 constexpr int NT = 256;
-constexpr unsigned kSent = 0xFFFFFFFFu;
 constexpr int kSpinLimit = 1 << 21;
 constexpr int kMaxRT = 4;  // N <= 64 (four 16-row MFMA tiles)
 constexpr int kMaxCT = 4;  // <= 64 gate columns per workgroup
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool ready4(u32x4 v) {
-  return (v[0] != kSent) & (v[1] != kSent) & (v[2] != kSent) & (v[3] != kSent);
-}
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void *base, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, bytes, 0x00020000);
@@ -52,31 +47,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void *base, unsigne
 __device__ __forceinline__ u32x4 ld_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
   return __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 16 /* sc1 */);
 }
-
-// Re-poll one 16-byte fragment until it holds no sentinel (bounded spin).
-__device__ __forceinline__ u32x4 settle(__amdgpu_buffer_rsrc_t r, unsigned off, u32x4 v,
-                                        unsigned *err, int &bad) {
-  int spins = 0;
-  while (!bad && !ready4(v)) {
-    if (++spins > kSpinLimit) { bad = 1; break; }
-    if ((spins & 255) == 0 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-      bad = 1;
-      break;
-    }
-    __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-    v = ld_sc1(r, off);
-  }
-  return v;
-}
-
-__device__ __forceinline__ void publish(float *p, float v) {
-  unsigned u = __float_as_uint(v);
-  if (u == kSent) u = 0x7FC00000u;  // never publish the sentinel bit pattern
-  __hip_atomic_store(reinterpret_cast<unsigned *>(p), u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
 struct RecParams {
   int T, N, H, dirs, U, nwg, ncol, Npad;
@@ -87,21 +57,25 @@ struct RecParams {
   long r_off;       // R within a pseudo-layer block
   long bR_off;      // bR within a pseudo-layer block
   float *G;         // [T*N][dirs*nW*H] pre-activations -> activations
-  float *y;         // [T*N][dirs*H] output / h exchange (sentinel pre-filled)
+  float *y;         // [T*N][dirs*H] output
   float *aux;       // LSTM: c ; GRU: R_n h + b_Rn   [T*N][dirs*H]
   const float *dy;  // backward: [T*N][dirs*H]
-  float *E;         // backward: dGates (recurrent part) exchange [T*N][dirs*nW*H]
+  float *E;         // backward: dGates (recurrent part) [T*N][dirs*nW*H]
   float *DX;        // backward GRU: dGates (input part); == E otherwise
   float *bias;      // backward: bias partial sums [dirs][2][nW*H]
-  unsigned *flags;  // flag protocol: [dirs][nwg] step epochs, zeroed before launch
+  unsigned *flags;  // generic: [dirs][nwg] step epochs; v6: flag6; zeroed before launch
   unsigned *err;
-  int sync;         // kSyncData / kSyncFlag
+  // unused: the place of a retired field.  Taking it out moves every field
+  // below by 8 bytes, and the v6 kernels' scalar argument loads then merge
+  // differently: their object code, compared across cleanups of this header,
+  // would change.
+  int kernarg_hold_;
   unsigned long long *trace;  // optional: [kTraceSteps][grid][8] s_memrealtime stamps
-  int allow_local;  // v4: hand off through the shared L2 when placement allows it
-  int xpd;          // v4: XCD slots per direction (nwg = 32 * xpd workgroups)
+  int allow_local;  // pinned v6: hand off through the shared L2 when placement allows it
+  int xpd;          // generic: XCD slots per direction (0: plain block mapping); v6: 1 when XCD-pinned
   int ring;         // v6: hand-off images reused every `ring` steps (0: one image per step; forward: ring after the T step images)
   int fcopy;        // v6 forward, XCD-pinned: h images also written through (sc1) per step for a streamed projection
-  float *xch;       // v4: per-step exchange images [T][dirs][KG][Npad][16] (workspace)
+  float *xch;       // generic: per-step exchange images [T][dirs][KG][Npad][16] (workspace)
   int poll_sleep;   // v6: s_sleep between flag polls
   int gla;          // v6 forward IO waves: steps ahead the G rows are fetched (3 or 7; 8 LDS slots)
   int e_sc1;        // v6 backward: dGates rows written through (sc1) for a streaming consumer
@@ -161,18 +135,13 @@ constexpr int kTraceSteps = 256, kTraceStride = 32;
       trc_[(long)(kk) * trg_ + (ph) + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime(); \
   } while (0)
 
-// Hand-off protocols (selected per launch; both placement-independent):
-//  kSyncData: the payload is the flag (sentinel-filled buffer, sc1 4-B stores,
-//             sc1 16-B loads re-polled until no sentinel is left).
-//  kSyncFlag: payload sc1 stores -> every storing wave s_waitcnt vmcnt(0) ->
-//             workgroup barrier -> ONE lane stores the step epoch (sc1) into
-//             the workgroup's flag word; consumers: wave 0 polls the nwg flag
-//             words of its direction with one sc1 load per lane, barrier, then
-//             every wave loads the payload with sc1 loads (MI355X_MICROARCH.md
-//             "Valid forms", row 1).  Polling traffic: 4 B per producer, not
-//             the whole payload.
-enum { kSyncData = 0, kSyncFlag = 1 };
-
+// Hand-off of the generic recurrences (placement-independent): payload sc1
+// stores (put) -> every storing wave s_waitcnt vmcnt(0) -> workgroup barrier
+// -> ONE lane stores the step epoch (sc1) into the workgroup's flag word
+// (signal_epoch); consumers: wave 0 polls the nwg flag words of its direction
+// with one sc1 load per lane, barrier (wait_flags), then every wave loads the
+// payload with sc1 loads (MI355X_MICROARCH.md "Valid forms", row 1).  Polling
+// traffic: 4 B per producer, not the whole payload.
 __device__ __forceinline__ void wait_flags(const unsigned *flags, int nwg, unsigned epoch,
                                            unsigned *err, int &bad, int *bad_lds) {
   if (threadIdx.x < 64) {
@@ -195,100 +164,8 @@ __device__ __forceinline__ void wait_flags(const unsigned *flags, int nwg, unsig
   if (*bad_lds) bad = 1;
 }
 
-__device__ __forceinline__ void signal_flag(unsigned *flag, unsigned epoch) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its sc1 stores
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// A-operand fragments of one step: rows n (RT 16-row tiles) x this wave's
-// k-groups {w, w+4, ...}, CH k-groups per pass, straight from the exchange
-// buffer into registers with sc1 16-B loads.  Returns false on timeout.
-template <int RT, int CH>
-__device__ __forceinline__ void load_frags(u32x4 (&af)[RT][CH], __amdgpu_buffer_rsrc_t rs, long ld,
-                                           long col0, int c0, int KG, int N, int sync, unsigned *err,
-                                           int &bad) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fr = lane & 15, fq = lane >> 4;
-#pragma unroll
-  for (int i = 0; i < CH; i++) {
-    const int kg = w + 4 * (c0 + i);
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) {
-      const int n = rt * 16 + fr;
-      af[rt][i] = u32x4{0u, 0u, 0u, 0u};
-      if (kg < KG && n < N) af[rt][i] = ld_sc1(rs, (unsigned)(((long)n * ld + col0 + kg * 16 + fq * 4) * 4));
-    }
-  }
-  if (sync == kSyncData) {
-#pragma unroll
-    for (int i = 0; i < CH; i++) {
-      const int kg = w + 4 * (c0 + i);
-#pragma unroll
-      for (int rt = 0; rt < RT; rt++) {
-        const int n = rt * 16 + fr;
-        if (kg < KG && n < N)
-          af[rt][i] = settle(rs, (unsigned)(((long)n * ld + col0 + kg * 16 + fq * 4) * 4), af[rt][i], err, bad);
-      }
-    }
-  }
-}
-
-// 16-byte write-through (sc1) publish of 4 consecutive units: every A-operand
-// fragment a consumer loads (4 consecutive k) is exactly one such store, so a
-// fragment is either all-sentinel or all-final (no tearing to re-poll).
-__device__ __forceinline__ floatx4 canon(floatx4 v) {
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-    if (__float_as_uint(v[i]) == kSent) v[i] = __uint_as_float(0x7FC00000u);
-  return v;
-}
-__device__ __forceinline__ void publish4(__amdgpu_buffer_rsrc_t r, unsigned off, floatx4 v) {
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, canon(v)), r, (int)off, 0, 16);
-}
 __device__ __forceinline__ floatx4 ld4(const float *p) { return *reinterpret_cast<const floatx4 *>(p); }
 __device__ __forceinline__ void st4(float *p, floatx4 v) { *reinterpret_cast<floatx4 *>(p) = v; }
-__device__ __forceinline__ floatx4 sigm4(floatx4 x) {
-  floatx4 r;
-#pragma unroll
-  for (int i = 0; i < 4; i++) r[i] = sigm(x[i]);
-  return r;
-}
-__device__ __forceinline__ floatx4 tanh4(floatx4 x) {
-  floatx4 r;
-#pragma unroll
-  for (int i = 0; i < 4; i++) r[i] = tanhf(x[i]);
-  return r;
-}
-
-// Poll every not-yet-valid fragment of this lane in batches: all re-loads of
-// a round are in flight together, so a round costs one memory round trip.
-template <int RT, int CH>
-__device__ __forceinline__ void settle_all(u32x4 (&af)[RT][CH], __amdgpu_buffer_rsrc_t rs, long ld,
-                                           long col0, int c0, int KG, int N, unsigned *err, int &bad) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, fr = lane & 15, fq = lane >> 4;
-  for (int round = 0; !bad; round++) {
-    int pending = 0;
-#pragma unroll
-    for (int i = 0; i < CH; i++) {
-      const int kg = w + 4 * (c0 + i);
-#pragma unroll
-      for (int rt = 0; rt < RT; rt++) {
-        const int n = rt * 16 + fr;
-        if (kg < KG && n < N && !ready4(af[rt][i])) {
-          af[rt][i] = ld_sc1(rs, (unsigned)(((long)n * ld + col0 + kg * 16 + fq * 4) * 4));
-          pending++;
-        }
-      }
-    }
-    if (!pending) break;
-    if (round > kSpinLimit ||
-        ((round & 255) == 255 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-      bad = 1;
-      break;
-    }
-    asm volatile("" ::: "memory");
-  }
-}
 
 __device__ __forceinline__ unsigned xcc_id() {
   unsigned v;

@@ -10,7 +10,7 @@ namespace kctc {
 struct RecScope {
   ~RecScope() { none(); }
   void enqueued(unsigned *flags, int workgroups);  // its flag area (RecParams::flags), dirs * nwg * rg
-  void none();  // (also after a v3 / v4 recurrence: no side launches)
+  void none();  // (also after a generic recurrence: no side launches)
 };
 // `side` waits until every workgroup of the recurrence in flight is resident;
 // whatever is enqueued on it afterwards may run beside that recurrence

@@ -1,388 +1,41 @@
-// rec_generic.hip -- the v3 (rnn_*_rec) and v4 (rnn_*_rec4: fp32 MFMA, XCD-slot
-// all-gather) recurrences, for the shapes v6 does not compile.  Host: rnn.hip.
+// rec_generic.hip -- the generic recurrences (rnn_fwd_rec / rnn_bwd_rec: fp32
+// MFMA, all-gather of h or dGates per step), for the shapes v6 does not
+// compile.  Host: rnn.hip.
 #include "rec_common.h"
 
 namespace kctc {
 namespace {
 
 // ---------------------------------------------------------------------------
-// forward recurrence
+// generic recurrences: all-gather hand-off, fp32 MFMA
 // ---------------------------------------------------------------------------
-template <int MODE, int RT>
-__global__ __launch_bounds__(NT, 1) void rnn_fwd_rec(RecParams p) {
-  REC_TRACE_INIT;
-  constexpr int NW = MODE == kLstm ? 4 : MODE == kGru ? 3 : 1;
-  constexpr int CH = 32 / RT;  // k-groups per wave per pass (<= 32 A-fragment registers x4)
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds;
-  const int H = p.H, U = p.U, N = p.N, T = p.T, ncol = p.ncol;
-  const int LDR = H + 4;
-  const int d = blockIdx.x / p.nwg, g = blockIdx.x % p.nwg, u0 = g * U;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
-  const int CT = ncol / 16;
-  const long ldy = (long)p.dirs * H, ldg = (long)p.dirs * NW * H;
-  float *Rs = smem;                      // [ncol][LDR]
-  float *red = Rs + (long)ncol * LDR;    // [4][Npad][ncol]
-  const float *Wd = p.w + d * p.pl_stride;
-  const float *R = Wd + p.r_off;
-  if (tid == 0) bad_lds = 0;
-  for (int idx = tid; idx < ncol * H; idx += NT) {
-    const int c = idx / H, k = idx - c * H;
-    float v = 0.f;
-    if (c < NW * U) {
-      const int gt = c / U, u = c - gt * U;
-      v = R[(long)(gt * H + u0 + u) * H + k];
-    }
-    Rs[c * LDR + k] = v;
-  }
-  // pointwise item of this thread: row n, units u0+4q .. u0+4q+3
-  const int Q = U / 4, items = N * Q;
-  const bool has_item = tid < items;
-  const int in_ = has_item ? tid / Q : 0, iq = has_item ? tid - in_ * Q : 0;
-  const int ucol = u0 + 4 * iq;
-  floatx4 cst = {0.f, 0.f, 0.f, 0.f}, hpv = cst, gin[NW], bR[NW];
-#pragma unroll
-  for (int q = 0; q < NW; q++) {
-    bR[q] = (MODE == kGru && has_item) ? ld4(Wd + p.bR_off + q * H + ucol) : floatx4{0.f, 0.f, 0.f, 0.f};
-    gin[q] = floatx4{0.f, 0.f, 0.f, 0.f};
-  }
-  if (has_item) {  // prefetch the input projection of the first step
-    const int t = d == 0 ? 0 : T - 1;
-#pragma unroll
-    for (int q = 0; q < NW; q++) gin[q] = ld4(p.G + ((long)t * N + in_) * ldg + (long)d * NW * H + q * H + ucol);
-  }
-  __syncthreads();
-  int bad = 0;
-  const int KG = H / 16;
-  const int KGW = (KG + 3) / 4;  // k-groups per wave
-  const unsigned step_bytes = (unsigned)((long)N * ldy * sizeof(float));
-  unsigned *myflag = p.flags + d * p.nwg + g;
-  for (int k = 0; k < T; k++) {
-    const int t = d == 0 ? k : T - 1 - k, tp = d == 0 ? t - 1 : t + 1;
-    floatx4 acc[RT][kMaxCT];
-#pragma unroll
-    for (int a = 0; a < RT; a++)
-#pragma unroll
-      for (int b = 0; b < kMaxCT; b++) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-    REC_TRACE(k, 0);
-    if (k > 0) {
-      if (p.sync == kSyncFlag) wait_flags(p.flags + d * p.nwg, p.nwg, (unsigned)k, p.err, bad, &bad_lds);
-      REC_TRACE(k, 1);
-      const auto rs = rsrc(p.y + (long)tp * N * ldy, step_bytes);
-      for (int c0 = 0; c0 < KGW; c0 += CH) {
-        u32x4 af[RT][CH];
-        load_frags<RT, CH>(af, rs, ldy, (long)d * H, c0, KG, N, kSyncFlag, p.err, bad);
-        if (p.sync == kSyncData) settle_all<RT, CH>(af, rs, ldy, (long)d * H, c0, KG, N, p.err, bad);
-        if (p.trace) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          REC_TRACE(k, 2);
-        }
-#pragma unroll
-        for (int i = 0; i < CH; i++) {
-          const int kg = w + 4 * (c0 + i);
-          if (kg < KG) {
-#pragma unroll
-            for (int ct = 0; ct < kMaxCT; ct++) {
-              if (ct < CT) {
-                const floatx4 b = ld4(Rs + (ct * 16 + fr) * LDR + kg * 16 + fq * 4);
-#pragma unroll
-                for (int s = 0; s < 4; s++)
-#pragma unroll
-                  for (int rt = 0; rt < RT; rt++)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(af[rt][i][s]), b[s],
-                                                                       acc[rt][ct], 0, 0, 0);
-              }
-            }
-          }
-        }
-      }
-    }
-    // cross-wave K reduction through LDS
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-      for (int ct = 0; ct < kMaxCT; ct++)
-        if (ct < CT)
-#pragma unroll
-          for (int r = 0; r < 4; r++)
-            red[((long)w * p.Npad + rt * 16 + fq * 4 + r) * ncol + ct * 16 + fr] = acc[rt][ct][r];
-    __syncthreads();
-    REC_TRACE(k, 3);
-    floatx4 act[NW], cnew = {0.f, 0.f, 0.f, 0.f};
-    const long yrow = ((long)t * N + in_) * ldy + (long)d * H + ucol;
-    if (has_item) {
-      floatx4 rh[NW];
-#pragma unroll
-      for (int q = 0; q < NW; q++) {
-        const int c = q * U + 4 * iq;
-        rh[q] = ((ld4(red + ((long)0 * p.Npad + in_) * ncol + c) + ld4(red + ((long)1 * p.Npad + in_) * ncol + c)) +
-                 ld4(red + ((long)2 * p.Npad + in_) * ncol + c)) + ld4(red + ((long)3 * p.Npad + in_) * ncol + c);
-      }
-      floatx4 h;
-      if (MODE == kLstm) {
-        act[0] = sigm4(gin[0] + rh[0]);
-        act[1] = sigm4(gin[1] + rh[1]);
-        act[2] = tanh4(gin[2] + rh[2]);
-        act[3] = sigm4(gin[3] + rh[3]);
-        cst = act[1] * cst + act[0] * act[2];
-        cnew = cst;
-        h = act[3] * tanh4(cst);
-      } else if (MODE == kGru) {
-        act[0] = sigm4(gin[0] + rh[0] + bR[0]);
-        act[1] = sigm4(gin[1] + rh[1] + bR[1]);
-        cnew = rh[2] + bR[2];
-        act[2] = tanh4(gin[2] + act[0] * cnew);
-        h = (1.f - act[1]) * act[2] + act[1] * hpv;
-        hpv = h;
-      } else {
-        const floatx4 pre = gin[0] + rh[0];
-        if (MODE == kRelu) {
-#pragma unroll
-          for (int i = 0; i < 4; i++) h[i] = fmaxf(pre[i], 0.f);
-        } else {
-          h = tanh4(pre);
-        }
-      }
-      publish4(rsrc(p.y + (long)t * N * ldy, step_bytes), (unsigned)(((long)in_ * ldy + (long)d * H + ucol) * 4), h);
-    }
-    if (p.sync == kSyncFlag) signal_flag(myflag, (unsigned)(k + 1));
-    REC_TRACE(k, 4);
-    if (has_item) {
-      const long grow = ((long)t * N + in_) * ldg + (long)d * NW * H + ucol;
-      if (MODE == kLstm || MODE == kGru) {
-#pragma unroll
-        for (int q = 0; q < NW; q++) st4(p.G + grow + q * H, act[q]);
-        st4(p.aux + yrow, cnew);
-      }
-      if (k + 1 < T) {  // prefetch the next step's input projection
-        const int tn = d == 0 ? t + 1 : t - 1;
-#pragma unroll
-        for (int q = 0; q < NW; q++) gin[q] = ld4(p.G + ((long)tn * N + in_) * ldg + (long)d * NW * H + q * H + ucol);
-      }
-    }
-    __syncthreads();  // red[] is rewritten by the next step
-    REC_TRACE(k, 5);
-  }
-  if (bad && tid == 0) atomicOr(p.err, 1u);
-}
-
-// ---------------------------------------------------------------------------
-// backward-data recurrence
-// ---------------------------------------------------------------------------
-template <int MODE, int RT>
-__global__ __launch_bounds__(NT, 1) void rnn_bwd_rec(RecParams p) {
-  REC_TRACE_INIT;
-  constexpr int NW = MODE == kLstm ? 4 : MODE == kGru ? 3 : 1;
-  constexpr int CH = 32 / RT;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds;
-  const int H = p.H, U = p.U, N = p.N, T = p.T;
-  const int K = NW * H, LDK = K + 4;
-  const int d = blockIdx.x / p.nwg, g = blockIdx.x % p.nwg, u0 = g * U;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
-  const long ldy = (long)p.dirs * H, ldg = (long)p.dirs * NW * H;
-  float *RT_s = smem;                       // [U][LDK]: RT_s[u][kk] = R[kk][u0+u]
-  float *red = RT_s + (long)U * LDK;        // [4][Npad][16]
-  const float *Wd = p.w + d * p.pl_stride;
-  const float *R = Wd + p.r_off;
-  if (tid == 0) bad_lds = 0;
-  for (int idx = tid; idx < U * K; idx += NT) {
-    const int kk = idx / U, u = idx - kk * U;
-    RT_s[u * LDK + kk] = R[(long)kk * H + u0 + u];
-  }
-  const int Q = U / 4, items = N * Q;
-  const bool has_item = tid < items;
-  const int in_ = has_item ? tid / Q : 0, iq = has_item ? tid - in_ * Q : 0;
-  const int ucol = u0 + 4 * iq;
-  const floatx4 z4 = {0.f, 0.f, 0.f, 0.f};
-  floatx4 carry = z4;  // LSTM: dc carried to the previous step; GRU: dh*z direct term
-  floatx4 bsx[NW], bsh[NW], pg[NW], pdy = z4, pa = z4, pap = z4;
-#pragma unroll
-  for (int q = 0; q < NW; q++) bsx[q] = bsh[q] = pg[q] = z4;
-  auto prefetch = [&](int k) {
-    if (!has_item) return;
-    const int t = d == 0 ? k : T - 1 - k, tp = d == 0 ? t - 1 : t + 1;
-    const long yrow = ((long)t * N + in_) * ldy + (long)d * H + ucol;
-    const long grow = ((long)t * N + in_) * ldg + (long)d * NW * H + ucol;
-    const long prow = ((long)tp * N + in_) * ldy + (long)d * H + ucol;
-    pdy = ld4(p.dy + yrow);
-    if (MODE == kLstm || MODE == kGru) {
-#pragma unroll
-      for (int q = 0; q < NW; q++) pg[q] = ld4(p.G + grow + q * H);
-      pa = ld4(p.aux + yrow);
-    }
-    if (MODE == kLstm) pap = k > 0 ? ld4(p.aux + prow) : z4;
-    else if (MODE == kGru) pap = k > 0 ? ld4(p.y + prow) : z4;
-    else pap = ld4(p.y + yrow);
-  };
-  prefetch(T - 1);
-  __syncthreads();
-  int bad = 0;
-  const int KG = K / 16;
-  const int KGW = (KG + 3) / 4;
-  const unsigned step_bytes = (unsigned)((long)N * ldg * sizeof(float));
-  unsigned *myflag = p.flags + d * p.nwg + g;
-  for (int k = T - 1; k >= 0; k--) {
-    const int t = d == 0 ? k : T - 1 - k;       // forward-order index k
-    const int tn = d == 0 ? t + 1 : t - 1;      // processed just before (k+1)
-    const unsigned epoch = (unsigned)(T - k);   // number of steps published so far
-    floatx4 acc[RT];
-#pragma unroll
-    for (int a = 0; a < RT; a++) acc[a] = z4;
-    const int ks = T - 1 - k;
-    REC_TRACE(ks, 0);
-    if (k < T - 1) {
-      if (p.sync == kSyncFlag) wait_flags(p.flags + d * p.nwg, p.nwg, epoch - 1, p.err, bad, &bad_lds);
-      REC_TRACE(ks, 1);
-      const auto rs = rsrc(p.E + (long)tn * N * ldg, step_bytes);
-      for (int c0 = 0; c0 < KGW; c0 += CH) {
-        u32x4 af[RT][CH];
-        load_frags<RT, CH>(af, rs, ldg, (long)d * K, c0, KG, N, kSyncFlag, p.err, bad);
-        if (p.sync == kSyncData) settle_all<RT, CH>(af, rs, ldg, (long)d * K, c0, KG, N, p.err, bad);
-        if (p.trace) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          REC_TRACE(ks, 2);
-        }
-#pragma unroll
-        for (int i = 0; i < CH; i++) {
-          const int kg = w + 4 * (c0 + i);
-          if (kg < KG) {
-            floatx4 b = z4;
-            if (fr < U) b = ld4(RT_s + fr * LDK + kg * 16 + fq * 4);
-#pragma unroll
-            for (int s = 0; s < 4; s++)
-#pragma unroll
-              for (int rt = 0; rt < RT; rt++)
-                acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(af[rt][i][s]), b[s], acc[rt], 0, 0, 0);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) red[((long)w * p.Npad + rt * 16 + fq * 4 + r) * 16 + fr] = acc[rt][r];
-    __syncthreads();
-    REC_TRACE(ks, 3);
-    floatx4 dxk[NW];
-    const long grow = ((long)t * N + in_) * ldg + (long)d * NW * H + ucol;
-    const auto rsE = rsrc(p.E + (long)t * N * ldg, step_bytes);
-    const unsigned eoff = (unsigned)(((long)in_ * ldg + (long)d * NW * H + ucol) * 4);
-    if (has_item) {
-      const floatx4 dhr = ((ld4(red + ((long)0 * p.Npad + in_) * 16 + 4 * iq) + ld4(red + ((long)1 * p.Npad + in_) * 16 + 4 * iq)) +
-                           ld4(red + ((long)2 * p.Npad + in_) * 16 + 4 * iq)) + ld4(red + ((long)3 * p.Npad + in_) * 16 + 4 * iq);
-      floatx4 dh = pdy + dhr;
-      if (MODE == kLstm) {
-        const floatx4 ig = pg[0], fg = pg[1], gg = pg[2], og = pg[3];
-        const floatx4 tc = tanh4(pa);
-        const floatx4 dO = dh * tc;
-        const floatx4 dc = dh * og * (1.f - tc * tc) + carry;
-        const floatx4 dpi = dc * gg * ig * (1.f - ig);
-        const floatx4 dpf = dc * pap * fg * (1.f - fg);
-        const floatx4 dpg = dc * ig * (1.f - gg * gg);
-        const floatx4 dpo = dO * og * (1.f - og);
-        carry = dc * fg;
-        publish4(rsE, eoff, dpi);
-        publish4(rsE, eoff + 4 * H, dpf);
-        publish4(rsE, eoff + 8 * H, dpg);
-        publish4(rsE, eoff + 12 * H, dpo);
-        bsx[0] += dpi; bsx[1] += dpf; bsx[2] += dpg; bsx[3] += dpo;
-      } else if (MODE == kGru) {
-        dh += carry;
-        const floatx4 r = pg[0], z = pg[1], nn = pg[2];
-        const floatx4 dn = dh * (1.f - z), dz = dh * (pap - nn);
-        const floatx4 dpn = dn * (1.f - nn * nn);
-        const floatx4 dpr = dpn * pa * r * (1.f - r);
-        const floatx4 dpz = dz * z * (1.f - z);
-        carry = dh * z;
-        dxk[0] = dpr; dxk[1] = dpz; dxk[2] = dpn;
-        publish4(rsE, eoff, dpr);
-        publish4(rsE, eoff + 4 * H, dpz);
-        publish4(rsE, eoff + 8 * H, dpn * r);
-        bsx[0] += dpr; bsx[1] += dpz; bsx[2] += dpn;
-        bsh[0] += dpr; bsh[1] += dpz; bsh[2] += dpn * r;
-      } else {
-        floatx4 der;
-#pragma unroll
-        for (int i = 0; i < 4; i++) der[i] = MODE == kRelu ? (pap[i] > 0.f ? 1.f : 0.f) : (1.f - pap[i] * pap[i]);
-        const floatx4 dp = dh * der;
-        publish4(rsE, eoff, dp);
-        bsx[0] += dp;
-      }
-    }
-    if (p.sync == kSyncFlag) signal_flag(myflag, epoch);
-    REC_TRACE(ks, 4);
-    if (MODE == kGru && has_item) {
-#pragma unroll
-      for (int q = 0; q < NW; q++) st4(p.DX + grow + q * H, dxk[q]);
-    }
-    if (k > 0) prefetch(k - 1);
-    __syncthreads();
-    REC_TRACE(ks, 5);
-  }
-  // bias partial sums: reduce over n in a fixed order through LDS
-  float *bs = red;  // reuse: [2][N][U][NW] floats
-  if (has_item) {
-#pragma unroll
-    for (int q = 0; q < NW; q++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const long base = ((long)in_ * U + 4 * iq + i) * NW + q;
-        bs[base] = bsx[q][i];
-        bs[(long)N * U * NW + base] = (MODE == kGru) ? bsh[q][i] : bsx[q][i];
-      }
-  }
-  __syncthreads();
-  for (int q = tid; q < 2 * NW * U; q += NT) {
-    const int part = q / (NW * U), rem = q - part * NW * U, gt = rem / U, u = rem - gt * U;
-    float s = 0.f;
-    for (int n = 0; n < N; n++) s += bs[(long)part * N * U * NW + ((long)n * U + u) * NW + gt];
-    p.bias[((long)d * 2 + part) * NW * H + gt * H + u0 + u] = s;
-  }
-  if (bad && tid == 0) atomicOr(p.err, 1u);
-}
-
-
-// ---------------------------------------------------------------------------
-// v4: XCD-local recurrences
-// ---------------------------------------------------------------------------
-// Grid = 8 * nwg; block b works as (dir = b & 7, g = b >> 3) when b & 7 < dirs,
-// the others exit at once.  Under the observed round-robin dispatch the nwg
-// (<= 32) workgroups of one direction then share one XCD and its L2, so the
-// per-step all-gather of h (or dGates) is served by that L2 instead of the
-// fabric.  This is checked, never assumed: every workgroup publishes its
-// HW_REG_XCC_ID through the placement-independent form, and only when ALL
-// workgroups of a direction read one id does that direction hand off through
-// its L2 (plain payload and flag stores, which stay in the shared L2; sc1
-// loads, which bypass the reading CU's L1).  Otherwise it uses the
-// placement-independent form throughout (sc1 write-through payload and flag
-// stores after every storing wave's vmcnt(0) and a barrier, sc1 loads:
-// MI355X_MICROARCH.md "Valid forms", row 1).  Either way a step is
+// Block mapping (block_of): with p.xpd > 0 the grid is 8 * ceil(nwg / xpd) and
+// block b works in XCD slot b & 7 -- direction slot / xpd, workgroup
+// (b >> 3) * xpd + slot % xpd -- so that under round-robin dispatch the
+// workgroups of one direction share xpd XCDs and their L2; blocks past dirs or
+// nwg exit at once.  p.xpd == 0 (no U gives a direction whole slots): grid
+// dirs * nwg, block b -> (b / nwg, b % nwg).  The slots are a placement hint
+// only: the hand-off is the placement-independent form throughout (sc1
+// write-through payload and flag stores after every storing wave's vmcnt(0)
+// and a barrier, sc1 loads: MI355X_MICROARCH.md "Valid forms", row 1).  A
+// step is
 //   wait for the direction's nwg epoch flags (one sc1 poll per lane, wave 0)
 //   -> sc1 16-B loads of the previous step straight into MFMA A registers
 //   -> v_mfma_f32_16x16x4_f32 over the LDS-resident R slice (K split over
 //      the 4 waves, reduced through LDS)
 //   -> pointwise cell math, one (n, unit) element per thread
 //   -> payload stores -> vmcnt(0) -> barrier -> lane 0 epoch flag.
-// Epoch 1 is the placement probe; step k publishes epoch k + 2.
-
-// Placement probe: returns 1 iff every workgroup of direction d is on this XCD.
-__device__ int probe_local(const RecParams &p, int d, int g, unsigned *myflag, int &bad, int *bad_lds,
-                           int *loc_lds) {
-  unsigned *xt = p.flags + 512 + d * p.nwg;
-  const unsigned me = xcc_id() + 1u;
-  if (threadIdx.x == 0) __hip_atomic_store(xt + g, me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  signal_epoch(myflag, 1u, 0);
-  wait_flags(p.flags + d * p.nwg, p.nwg, 1u, p.err, bad, bad_lds);
-  if (threadIdx.x < 64) {
-    bool ok = true;
-    for (int i = threadIdx.x; i < p.nwg; i += 64)
-      ok &= __hip_atomic_load(xt + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == me;
-    const bool all = __all(ok);
-    if (threadIdx.x == 0) *loc_lds = (all && p.allow_local) ? 1 : 0;
+// Step k publishes epoch k + 2.
+__device__ __forceinline__ bool block_of(const RecParams &p, int &d, int &g) {
+  if (p.xpd > 0) {
+    const int slot = blockIdx.x & 7;
+    d = slot / p.xpd;
+    g = (blockIdx.x >> 3) * p.xpd + slot % p.xpd;
+  } else {
+    d = blockIdx.x / p.nwg;
+    g = blockIdx.x % p.nwg;
   }
-  __syncthreads();
-  return *loc_lds;
+  return d < p.dirs && g < p.nwg;
 }
 
 // Exchange image of one step, fragment-major: [dirs][KG][Npad][16] floats
@@ -428,10 +81,15 @@ __device__ __forceinline__ void fwd_step_mfma(floatx4 (&acc)[RT][kMaxCT], __amdg
 
 // Backward: acc[RT] = dG_{t+1}[rows][kk] * R^T_slice[kk][units] over all nW*H
 // kk (wave w: k-groups w, w+4, ...); NA accumulator sets interleaved so no
-// MFMA waits on its predecessor, summed in a fixed order.
+// MFMA waits on its predecessor, summed in a fixed order.  RT_s holds U rows:
+// a lane's B fragment comes from row br = fr, or row 0 for a lane past them
+// (fr >= U).  Output column fr of the MFMA depends on B column fr alone, and
+// the cell reads the columns below U only, so what such a lane multiplies
+// never reaches a result; it only has to lie inside the image.  (Zeroing it,
+// by a branch or a select per load, measured 3 to 11 % slower on LSTM-384.)
 template <int RT, int KGW>
 __device__ __forceinline__ void bwd_step_mfma(floatx4 (&acc)[RT], __amdgpu_buffer_rsrc_t rs, long dbase, int Npad,
-                                              const float *RT_s, int LDK, int w, int fr, int fq) {
+                                              const float *RT_s, int LDK, int br, int w, int fr, int fq) {
   constexpr int NA = (KGW % 4 == 0) ? 4 : (KGW % 2 == 0 ? 2 : 1);
   u32x4 af[KGW][RT];
 #pragma unroll
@@ -444,7 +102,7 @@ __device__ __forceinline__ void bwd_step_mfma(floatx4 (&acc)[RT], __amdgpu_buffe
   for (int a = 0; a < NA; a++)
 #pragma unroll
     for (int rt = 0; rt < RT; rt++) part[a][rt] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const float *brow = RT_s + fr * LDK + fq * 4;
+  const float *brow = RT_s + br * LDK + fq * 4;
 #pragma unroll
   for (int i0 = 0; i0 < KGW; i0 += NA) {
     floatx4 b[NA];
@@ -468,7 +126,7 @@ __device__ __forceinline__ void bwd_step_mfma(floatx4 (&acc)[RT], __amdgpu_buffe
   }
 }
 
-// generic (runtime trip count) versions of the same bodies
+// runtime trip count versions of the same bodies
 template <int RT>
 __device__ __forceinline__ void fwd_step_generic(floatx4 (&acc)[RT][kMaxCT], __amdgpu_buffer_rsrc_t rs, long dbase,
                                                  int Npad, int KG, int CT, const float *Rs, int LDR, int w, int fr,
@@ -493,13 +151,13 @@ __device__ __forceinline__ void fwd_step_generic(floatx4 (&acc)[RT][kMaxCT], __a
 }
 template <int RT>
 __device__ __forceinline__ void bwd_step_generic(floatx4 (&acc)[RT], __amdgpu_buffer_rsrc_t rs, long dbase, int Npad,
-                                                 int KG, const float *RT_s, int LDK, int w, int fr, int fq) {
+                                                 int KG, const float *RT_s, int LDK, int br, int w, int fr, int fq) {
   for (int kg = w; kg < KG; kg += 4) {
     u32x4 af[RT];
 #pragma unroll
     for (int rt = 0; rt < RT; rt++)
       af[rt] = ld_sc1(rs, (unsigned)((dbase + ((long)kg * Npad + rt * 16 + fr) * 16 + fq * 4) * 4));
-    const floatx4 b = ld4(RT_s + fr * LDK + kg * 16 + fq * 4);
+    const floatx4 b = ld4(RT_s + br * LDK + kg * 16 + fq * 4);
 #pragma unroll
     for (int s = 0; s < 4; s++)
 #pragma unroll
@@ -513,13 +171,13 @@ __device__ __forceinline__ void bwd_step_generic(floatx4 (&acc)[RT], __amdgpu_bu
 // right AFTER the step's hand-off loads have been consumed, never in front of
 // them: a wave's vector memory operations complete in issue order.
 template <int MODE, int RT>
-__global__ __launch_bounds__(NT, 1) void rnn_fwd_rec4(RecParams p) {
+__global__ __launch_bounds__(NT, 1) void rnn_fwd_rec(RecParams p) {
   REC_TRACE_INIT;
   constexpr int NW = MODE == kLstm ? 4 : MODE == kGru ? 3 : 1;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds, loc_lds;
-  const int slot = blockIdx.x & 7, d = slot / p.xpd, g = (blockIdx.x >> 3) * p.xpd + slot % p.xpd;
-  if (d >= p.dirs || g >= p.nwg) return;
+  __shared__ int bad_lds;
+  int d, g;
+  if (!block_of(p, d, g)) return;
   const int H = p.H, U = p.U, N = p.N, T = p.T, ncol = p.ncol, Npad = p.Npad;
   const int LDR = H + 4;
   const int u0 = g * U;
@@ -583,9 +241,9 @@ __global__ __launch_bounds__(NT, 1) void rnn_fwd_rec4(RecParams p) {
     }
   }
   gin_load(d == 0 ? 0 : T - 1, gin);
+  __syncthreads();  // the R slice and bad_lds are in place
   int bad = 0;
   unsigned *myflag = p.flags + d * p.nwg + g;
-  const int local = probe_local(p, d, g, myflag, bad, &bad_lds, &loc_lds);
   const int KGW = KG / 4;
   const int fast = (KG % 4 == 0 && KGW * RT <= 32 && (KGW == 8 || KGW == 4)) ? CT * 100 + KGW / 2 : 0;
   const long dbase = (long)d * KG * Npad * 16;
@@ -668,9 +326,9 @@ __global__ __launch_bounds__(NT, 1) void rnn_fwd_rec4(RecParams p) {
       }
       hval[j] = h;
       const int uu = u0 + u;
-      put(xt + xoff(d, uu >> 4, n, uu & 15, KG, Npad), h, local);
+      put(xt + xoff(d, uu >> 4, n, uu & 15, KG, Npad), h, 0);
     }
-    signal_epoch(myflag, (unsigned)(k + 2), local);
+    signal_epoch(myflag, (unsigned)(k + 2), 0);
     REC_TRACE(k, 4);
 #pragma unroll
     for (int j = 0; j < kMaxEPT; j++)
@@ -685,13 +343,13 @@ __global__ __launch_bounds__(NT, 1) void rnn_fwd_rec4(RecParams p) {
 }
 
 template <int MODE, int RT>
-__global__ __launch_bounds__(NT, 1) void rnn_bwd_rec4(RecParams p) {
+__global__ __launch_bounds__(NT, 1) void rnn_bwd_rec(RecParams p) {
   REC_TRACE_INIT;
   constexpr int NW = MODE == kLstm ? 4 : MODE == kGru ? 3 : 1;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int bad_lds, loc_lds;
-  const int slot = blockIdx.x & 7, d = slot / p.xpd, g = (blockIdx.x >> 3) * p.xpd + slot % p.xpd;
-  if (d >= p.dirs || g >= p.nwg) return;
+  __shared__ int bad_lds;
+  int d, g;
+  if (!block_of(p, d, g)) return;
   const int H = p.H, U = p.U, N = p.N, T = p.T, Npad = p.Npad;
   const int K = NW * H, LDK = K + 4;
   const int KG = K / 16;
@@ -699,14 +357,15 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_rec4(RecParams p) {
   const int u0 = g * U;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, fr = lane & 15, fq = lane >> 4;
   const long ldy = (long)p.dirs * H, ldg = (long)p.dirs * NW * H;
-  float *RT_s = smem;                       // [16][LDK]: RT_s[u][kk] = R[kk][u0+u], rows >= U zero
-  float *red = RT_s + (long)16 * LDK;       // [4][Npad][16]
+  const int br = fr < U ? fr : 0;           // the row of RT_s this lane's B fragments come from (bwd_step_mfma)
+  float *RT_s = smem;                       // [U][LDK]: RT_s[u][kk] = R[kk][u0+u]
+  float *red = RT_s + (long)U * LDK;        // [4][Npad][16]
   const float *Wd = p.w + d * p.pl_stride;
   const float *R = Wd + p.r_off;
   if (tid == 0) bad_lds = 0;
-  for (int idx = tid; idx < 16 * K; idx += NT) {
-    const int kk = idx / 16, u = idx - kk * 16;
-    RT_s[u * LDK + kk] = u < U ? R[(long)kk * H + u0 + u] : 0.f;
+  for (int idx = tid; idx < U * K; idx += NT) {
+    const int kk = idx / U, u = idx - kk * U;
+    RT_s[u * LDK + kk] = R[(long)kk * H + u0 + u];
   }
   const int items = N * U;
   // per element: current step's operands (c*), the next step's (n*), and the
@@ -766,9 +425,9 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_rec4(RecParams p) {
   };
   prefetch(T - 1);
   rotate();
+  __syncthreads();  // the R^T slice and bad_lds are in place
   int bad = 0;
   unsigned *myflag = p.flags + d * p.nwg + g;
-  const int local = probe_local(p, d, g, myflag, bad, &bad_lds, &loc_lds);
   const int KGW = KG / 4;
   const int fast = (KG % 4 == 0 && KGW * RT <= 32 &&
                     (KGW == 32 || KGW == 24 || KGW == 16 || KGW == 12 || KGW == 8 || KGW == 4)) ? KGW : 0;
@@ -787,13 +446,13 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_rec4(RecParams p) {
       REC_TRACE(ks, 1);
       const auto rs = rsrc(p.xch + (long)tn * xstep, (unsigned)(xstep * 4));
       switch (fast) {
-        case 32: bwd_step_mfma<RT, 32>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 24: bwd_step_mfma<RT, 24>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 16: bwd_step_mfma<RT, 16>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 12: bwd_step_mfma<RT, 12>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 8: bwd_step_mfma<RT, 8>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        case 4: bwd_step_mfma<RT, 4>(acc, rs, dbase, Npad, RT_s, LDK, w, fr, fq); break;
-        default: bwd_step_generic<RT>(acc, rs, dbase, Npad, KG, RT_s, LDK, w, fr, fq); break;
+        case 32: bwd_step_mfma<RT, 32>(acc, rs, dbase, Npad, RT_s, LDK, br, w, fr, fq); break;
+        case 24: bwd_step_mfma<RT, 24>(acc, rs, dbase, Npad, RT_s, LDK, br, w, fr, fq); break;
+        case 16: bwd_step_mfma<RT, 16>(acc, rs, dbase, Npad, RT_s, LDK, br, w, fr, fq); break;
+        case 12: bwd_step_mfma<RT, 12>(acc, rs, dbase, Npad, RT_s, LDK, br, w, fr, fq); break;
+        case 8: bwd_step_mfma<RT, 8>(acc, rs, dbase, Npad, RT_s, LDK, br, w, fr, fq); break;
+        case 4: bwd_step_mfma<RT, 4>(acc, rs, dbase, Npad, RT_s, LDK, br, w, fr, fq); break;
+        default: bwd_step_generic<RT>(acc, rs, dbase, Npad, KG, RT_s, LDK, br, w, fr, fq); break;
       }
     }
     asm volatile("" ::: "memory");
@@ -848,11 +507,11 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_rec4(RecParams p) {
 #pragma unroll
       for (int q = 0; q < NW; q++) {
         const int kk = q * H + uu;
-        put(xt + xoff(d, kk >> 4, n, kk & 15, KG, Npad), eg[j][q], local);
+        put(xt + xoff(d, kk >> 4, n, kk & 15, KG, Npad), eg[j][q], 0);
         bsx[j][q] += (MODE == kGru) ? dxk[j][q] : eg[j][q];
       }
     }
-    signal_epoch(myflag, (unsigned)(ks + 2), local);
+    signal_epoch(myflag, (unsigned)(ks + 2), 0);
     REC_TRACE(ks, 4);
     rotate();
     t_prev = t;
@@ -885,30 +544,24 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_rec4(RecParams p) {
   if (bad && tid == 0) atomicOr(p.err, 1u);
 }
 
-template <int MODE, int RT>
-const void *generic_of(bool fwd, int ver) {
-  auto *k = ver == 4 ? (fwd ? rnn_fwd_rec4<MODE, RT> : rnn_bwd_rec4<MODE, RT>)
-                     : (fwd ? rnn_fwd_rec<MODE, RT> : rnn_bwd_rec<MODE, RT>);
-  return reinterpret_cast<const void *>(k);
-}
 template <int MODE>
-const void *generic_of_mode(bool fwd, int ver, int rt) {
+const void *generic_of_mode(bool fwd, int rt) {
   switch (rt) {
-    case 1: return generic_of<MODE, 1>(fwd, ver);
-    case 2: return generic_of<MODE, 2>(fwd, ver);
-    case 3: return generic_of<MODE, 3>(fwd, ver);
-    default: return generic_of<MODE, 4>(fwd, ver);
+    case 1: return reinterpret_cast<const void *>(fwd ? rnn_fwd_rec<MODE, 1> : rnn_bwd_rec<MODE, 1>);
+    case 2: return reinterpret_cast<const void *>(fwd ? rnn_fwd_rec<MODE, 2> : rnn_bwd_rec<MODE, 2>);
+    case 3: return reinterpret_cast<const void *>(fwd ? rnn_fwd_rec<MODE, 3> : rnn_bwd_rec<MODE, 3>);
+    default: return reinterpret_cast<const void *>(fwd ? rnn_fwd_rec<MODE, 4> : rnn_bwd_rec<MODE, 4>);
   }
 }
 
 }  // namespace
 
-const void *rec_generic_kernel(bool fwd, int ver, int mode, int rt) {
+const void *rec_generic_kernel(bool fwd, int mode, int rt) {
   switch (mode) {
-    case kLstm: return generic_of_mode<kLstm>(fwd, ver, rt);
-    case kGru: return generic_of_mode<kGru>(fwd, ver, rt);
-    case kRelu: return generic_of_mode<kRelu>(fwd, ver, rt);
-    default: return generic_of_mode<kTanh>(fwd, ver, rt);
+    case kLstm: return generic_of_mode<kLstm>(fwd, rt);
+    case kGru: return generic_of_mode<kGru>(fwd, rt);
+    case kRelu: return generic_of_mode<kRelu>(fwd, rt);
+    default: return generic_of_mode<kTanh>(fwd, rt);
   }
 }
 

@@ -45,12 +45,13 @@
 //     for the streamed GEMMs outside the XCD (epoch_lines).
 // Every spin is bounded (3 s); a timeout sets the device error word, every
 // workgroup drains out and the train step fails loudly.
-// v4 (fp32 MFMA, XCD-slot all-gather) and v3 remain for the shapes v6 does
-// not compile (RELU / TANH, other H, N > 64).  This file is the host side of
-// the three entry points; which recurrence runs and where the workspace's
-// parts lie: rnn_plan.hip (plan_rec, RnnWs); what may run beside a
-// recurrence: rec_gate.hip; the kernels: rec6_fwd.hip, rec6_bwd.hip,
-// rec_generic.hip (v3 / v4), rec_common.h.
+// One generic kernel pair (fp32 MFMA, all-gather of h / dGates per step through
+// epoch flags, XCD-slot block mapping where the shape has whole slots) runs
+// the shapes v6 does not compile (RELU / TANH, other H).  This file is the
+// host side of the three entry points; which recurrence runs and where the
+// workspace's parts lie: rnn_plan.hip (plan_rec, RnnWs); what may run beside
+// a recurrence: rec_gate.hip; the kernels: rec6_fwd.hip, rec6_bwd.hip,
+// rec_generic.hip, rec_common.h.
 //
 // Semantics follow cuDNN v5 as used by CuDNNRecurrentComponent: hx = cx = 0,
 // dhy = dcy = 0 (SetBufferZero, nnet-cudnn-component.cc:494-506), all N
@@ -190,7 +191,7 @@ void launch_planned(const RnnDesc &d, const RecPlan &pl, bool fwd, RecParams &p,
                     hipStream_t s) {
   if (tr.arm(fwd ? "fwd" : "bwd", pl.grid)) p.trace = tr.dev;
   const void *k = pl.ver == 6 ? rec6_kernel(fwd, d.mode, d.prec, d.H, pl.c6)
-                              : rec_generic_kernel(fwd, pl.ver, d.mode, p.Npad / 16);
+                              : rec_generic_kernel(fwd, d.mode, p.Npad / 16);
   {
     ProfSpan ps(s, fwd ? "rnn_fwd_rec" : "rnn_bwd_rec");
     launch_rec(k, p, dim3(pl.grid), pl.nth, pl.lds, s);
@@ -611,7 +612,6 @@ void fwd_rec_params(RecParams &p, const RnnDesc &d, const RecPlan &pl, const Rnn
                     const RnnReserveLayout &lay, bool chained, bool rowchain, hipStream_t s) {
   const long TN = (long)p.T * p.N;
   p.ncol = (d.nw() * pl.U + 15) / 16 * 16;
-  p.sync = pl.ver == 4 ? kSyncFlag : kSyncData;
   p.allow_local = 0;
   p.xch = ws.xch();
   p.poll_sleep = 1;
@@ -703,7 +703,7 @@ int rnn_forward_training(const RnnDesc &d, hipStream_t s, int T, int N, const fl
   const RecPlan pl = plan_rec(d, N, true);
   if (!pl) return KRNN_NOT_SUPPORTED;
   const bool v6 = pl.ver == 6;
-  const int H = d.H, dirs = d.dirs;
+  const int dirs = d.dirs;
   const long TN = (long)T * N;
   float *res = static_cast<float *>(reserve);
   const float *in = x;
@@ -713,7 +713,6 @@ int rnn_forward_training(const RnnDesc &d, hipStream_t s, int T, int N, const fl
     float *out = last ? y : R0 + lay.out;
     const LayerW lw = layer_w(d, l);
     const float *wl = w + lw.pl0;
-    if (pl.ver == 3) KCTC_HIP_CHECK(hipMemsetAsync(out, 0xFF, sizeof(float) * TN * dirs * H, s));
     // (layer 0 may come projected: streamed by the previous component)
     if (!(l == 0 && input_projected)) project_input(d, ws, s, TN, l, in, in_rows, wl, lw, R0 + lay.G);
     RecParams p = rec_params(d, pl, ws, T, N, wl, lw, R0, lay, out, err, s);
@@ -809,7 +808,6 @@ int rnn_forward_inference_seq(const RnnDesc &d, hipStream_t s, int T, int N, con
     float *out = last ? y : R0 + lay.out;
     const LayerW lw = layer_w(d, l);
     const float *wl = w + lw.pl0;
-    if (pl.ver == 3) KCTC_HIP_CHECK(hipMemsetAsync(ys, 0xFF, sizeof(float) * TN * dirs * H, s));
     // no streamed hand-over and no packed input rows here: they read
     // un-shifted images
     if (dirs == 2) {
@@ -964,7 +962,6 @@ void bwd_rec_params(RecParams &p, const RnnDesc &d, const RecPlan &pl, const Rnn
   const long TN = (long)T * N;
   p.ncol = 16;
   p.dy = dy; p.E = E; p.DX = DX; p.bias = R0 + lay.bias;
-  p.sync = kSyncFlag;
   p.allow_local = 0;
   if (pl.ver != 6) {
     p.xch = ws.xch();
@@ -1092,7 +1089,7 @@ int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float
   const RnnWs ws(d, T, N, workspace);
   if (ws_bytes < ws.bytes()) return KRNN_BAD_PARAM;
   const bool v6 = pl.ver == 6;
-  const int NW = d.nw(), H = d.H, dirs = d.dirs;
+  const int dirs = d.dirs;
   const long TN = (long)T * N;
   float *res = static_cast<float *>(reserve);
   const float *dcur = dy;
@@ -1103,7 +1100,6 @@ int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float
     const float *wl = w + lw.pl0;
     float *E = R0 + lay.E;
     float *DX = d.mode == kGru ? R0 + lay.DX : E;
-    if (pl.ver == 3) KCTC_HIP_CHECK(hipMemsetAsync(E, 0xFF, sizeof(float) * TN * dirs * NW * H, s));
     RecParams p = rec_params(d, pl, ws, T, N, wl, lw, R0, lay, const_cast<float *>(out), err, s);
     // dx_l = sum_dir DX_dir W_dir   (lower layer's dy, or the caller's dx)
     float *dxl = (l == 0) ? dx : res + lay.per_layer * (l - 1) + lay.dout;

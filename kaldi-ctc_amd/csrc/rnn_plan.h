@@ -35,10 +35,10 @@ inline bool bf16_io(const RnnDesc &d) {
   return bf16_direct(d, 6) && d.layers == 1 && d.dirs == 2 && d.H % 32 == 0 && (2 * d.H) % 64 == 0 && d.pkio;
 }
 
-// CUs of one XCD (v4: one direction's workgroups per XCD slot; v6: a pinned
-// (row group, direction) on one XCD)
+// CUs of one XCD (generic: one direction's workgroups per XCD slot; v6: a
+// pinned (row group, direction) on one XCD)
 constexpr int kCusPerXcd = 32;
-// flag region: words 0..1023 (v3/v4 flags, placement ids, the named words of
+// flag region: words 0..1023 (generic flags, placement ids, the named words of
 // rec_common.h), then one 128-B line per (direction, workgroup) for v6
 constexpr size_t kFlagBytes = 4096 + 512 * 128;  // v6: up to 4 row groups x 2 dirs x 64 workgroups
 
@@ -55,8 +55,8 @@ struct PackLay {
 };
 
 // The workspace of (d, T, N): the split-K slabs of the weight-gradient GEMMs,
-// the recurrence flag words, the v4 exchange images (v6 forward: its step
-// images), then the pack area.  Built once per host call.
+// the recurrence flag words, the generic exchange images (v6 forward: its
+// step images), then the pack area.  Built once per host call.
 struct RnnWs {
   PackLay lay;
   long split_floats = 0;  // floats of the split slabs (dR's, then dW's)
@@ -74,13 +74,13 @@ struct RnnWs {
 // Which recurrence (d, N) runs in one direction of time, and how it is
 // launched.  ver 0: not supported (bf16 exists on v6 only; no U fits).
 struct RecPlan {
-  int ver = 0;   // 6 / 4 / 3
+  int ver = 0;   // 6: v6; 4: the generic kernels (rec_generic.hip)
   int U = 0;     // units per workgroup
   V6Cfg c6;      // ver == 6
   int nth = 0, nwg = 0;  // threads per workgroup, workgroups per (row group, direction)
   size_t lds = 0;        // dynamic LDS bytes
   int rg = 1, gs = 16;   // v6 row groups (RecParams::rg / gs)
-  int xpd = 0;           // RecParams::xpd: v4 XCD slots per direction; v6 1 when XCD-pinned; v3 1
+  int xpd = 0;           // RecParams::xpd: generic XCD slots per direction (0: plain mapping); v6 1 when XCD-pinned
   unsigned xcds = 0;     // XCDs a pinned v6 recurrence occupies (bit x: XCD x), else 0
   int wgs = 0;           // dirs * nwg * rg
   unsigned grid = 0;

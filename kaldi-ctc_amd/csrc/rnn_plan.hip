@@ -1,6 +1,7 @@
 // rnn_plan.hip -- layout and plan of the RNN host (rnn.hip): the training
 // reserve and the workspace (RnnWs), and which recurrence a (descriptor, N)
 // runs in each direction of time and how it is launched (plan_rec).
+#include <initializer_list>
 #include <map>
 
 #include "common.h"
@@ -59,7 +60,7 @@ static long drec_split_floats(const RnnDesc &d, int T, int N) {
 // never overlap)
 static size_t xch_bytes(const RnnDesc &d, int T, int N) {
   const long Npad = (N + 15) / 16 * 16;
-  // v4 images: 4 B x dirs x nW x H x Npad per step; the v6 forward's
+  // generic images: 4 B x dirs x nW x H x Npad per step; the v6 forward's
   // [2 dirs][H/32][hi, lo][16][32] halves per row group of <= 16 rows (at most
   // 2 Npad / 16 groups): 16 B x H x Npad.  + 2 steps: the v6 forward's ring of
   // hand-off images after its T step images
@@ -153,66 +154,48 @@ size_t fwd_lds_bytes(const RnnDesc &d, int N, int U) {
   const int ncol = (d.nw() * U + 15) / 16 * 16, Npad = (N + 15) / 16 * 16;
   return sizeof(float) * ((size_t)ncol * (d.H + 4) + 4 * (size_t)Npad * ncol);
 }
-size_t bwd_lds_bytes(const RnnDesc &d, int N, int U, int ver = 3) {
+size_t bwd_lds_bytes(const RnnDesc &d, int N, int U) {
   const int Npad = (N + 15) / 16 * 16;
-  return sizeof(float) * ((size_t)(ver == 4 ? 16 : U) * (d.nw() * d.H + 4) +
-                          std::max(4 * (size_t)Npad * 16, (size_t)2 * N * U * d.nw()));
+  return sizeof(float) * ((size_t)U * (d.nw() * d.H + 4) + std::max(4 * (size_t)Npad * 16, (size_t)2 * N * U * d.nw()));
 }
 
-// v3: pick U (units per workgroup): divides H, multiple of 4, blocks <= 256
-int pick_fwd_u(const RnnDesc &d, int N) {
-  auto ok = [&](int U) {
-    if (U < 4 || U % 4 || d.H % U || d.nw() * U > 16 * kMaxCT || N * U / 4 > NT) return false;
-    if ((long)d.dirs * (d.H / U) > 256) return false;
-    return fwd_lds_bytes(d, N, U) <= 160 * 1024;
-  };
-  // smallest U that keeps every workgroup resident (<= 256 = one per CU):
-  // per-step MFMA latency falls with U (measured: U=4 < 8 < 16 on BLSTM-512)
-  for (int U : {4, 8, 16})
-    if (ok(U)) return U;
-  return 0;
-}
-int pick_bwd_u(const RnnDesc &d, int N) {
-  auto ok = [&](int U) {
-    if (U < 4 || U % 4 || U > 16 || d.H % U || N * U / 4 > NT) return false;
-    if ((long)d.dirs * (d.H / U) > 256) return false;
-    return bwd_lds_bytes(d, N, U) <= 160 * 1024;
-  };
-  for (int U : {16, 8, 4})
-    if (ok(U)) return U;
-  return 0;
-}
-
-// v4 (XCD-local): nwg = H/U <= kCusPerXcd workgroups per direction, one XCD each.
-// XCD slots one direction spans for U units per workgroup (0: not a v4 shape)
-int v4_xpd(const RnnDesc &d, int U) {
-  if (U <= 0 || d.H % U) return 0;
+// Generic recurrences: U units per workgroup, nwg = H / U workgroups per direction.
+// XCD slots one direction spans for U (slot mapping: part of one slot, or 1,
+// 2, 4 or 8 whole slots of kCusPerXcd workgroups; 0: no such partition)
+int slot_xpd(const RnnDesc &d, int U) {
+  if (U <= 0 || d.H % U || d.dirs > 8) return 0;
   const int nwg = d.H / U;
-  if (nwg % kCusPerXcd) return nwg < kCusPerXcd && d.dirs <= 8 ? 1 : 0;
+  if (nwg % kCusPerXcd) return nwg < kCusPerXcd ? 1 : 0;
   const int x = nwg / kCusPerXcd;
   return (x == 1 || x == 2 || x == 4 || x == 8) && x * d.dirs <= 8 ? x : 0;
 }
-int pick_fwd_u4(const RnnDesc &d, int N) {
-  if (d.dirs > 8) return 0;
-  auto ok = [&](int U) {
-    return U >= 4 && U % 4 == 0 && v4_xpd(d, U) && d.nw() * U <= 16 * kMaxCT && N * U <= kMaxEPT * NT &&
-           fwd_lds_bytes(d, N, U) <= 160 * 1024;
+// U and RecPlan::xpd of (d, N) in one direction of time: the first U of the
+// slot-mapped order that fits, else the first of the plain-mapped order (xpd
+// 0, every workgroup resident: dirs * nwg <= 256 = one per CU); U 0: none fits
+struct GenericU {
+  int U = 0, xpd = 0;
+};
+GenericU pick_generic_u(const RnnDesc &d, int N, bool fwd) {
+  auto fits = [&](int U) {  // the kernels' own limits
+    if (d.H % U || N * U > kMaxEPT * NT) return false;
+    if (fwd) return d.nw() * U <= 16 * kMaxCT && fwd_lds_bytes(d, N, U) <= 160 * 1024;
+    return U <= 16 && bwd_lds_bytes(d, N, U) <= 160 * 1024;
   };
-  // measured on BLSTM-512 N=16 (1 x MI355X): U=8 (2 XCD slots per direction)
-  // 44 ms/step of forward recurrence, U=4 48, U=16 58
-  for (int U : {8, 16, 4, 32})
-    if (ok(U)) return U;
-  return 0;
-}
-int pick_bwd_u4(const RnnDesc &d, int N) {
-  if (d.dirs > 8) return 0;
-  auto ok = [&](int U) {
-    return U >= 4 && U <= 16 && U % 4 == 0 && v4_xpd(d, U) && N * U <= kMaxEPT * NT &&
-           bwd_lds_bytes(d, N, U, 4) <= 160 * 1024;
+  auto first = [&](std::initializer_list<int> order, bool slots) {
+    for (int U : order) {
+      if (!fits(U)) continue;
+      if (slots && slot_xpd(d, U)) return GenericU{U, slot_xpd(d, U)};
+      if (!slots && (long)d.dirs * (d.H / U) <= 256) return GenericU{U, 0};
+    }
+    return GenericU{};
   };
-  for (int U : {16, 8, 4})
-    if (ok(U)) return U;
-  return 0;
+  // forward, slot-mapped, measured on BLSTM-512 N=16 (1 x MI355X): U=8 (2 XCD
+  // slots per direction) 44 ms/step of forward recurrence, U=4 48, U=16 58
+  const GenericU c = fwd ? first({8, 16, 4, 32}, true) : first({16, 8, 4}, true);
+  if (c.U) return c;
+  // plain, forward: the smallest U that keeps every workgroup resident
+  // (per-step MFMA latency falls with U)
+  return fwd ? first({4, 8, 16}, false) : first({16, 8, 4}, false);
 }
 
 // v6 recurrences (LSTM / GRU): one configuration for a (shape, N):
@@ -351,15 +334,14 @@ unsigned xcd_mask(const RnnDesc &d, const V6Cfg &c6, bool fwd) {
 RecPlan plan_rec(const RnnDesc &d, int N, bool fwd) {
   RecPlan pl;
   const V6Cfg c6 = pick6(d, N, fwd);
-  const int U4 = c6 ? 0 : fwd ? pick_fwd_u4(d, N) : pick_bwd_u4(d, N);
-  const int ver = c6 ? 6 : U4 ? 4 : 3;
-  const int U = c6 ? c6.U : U4 ? U4 : fwd ? pick_fwd_u(d, N) : pick_bwd_u(d, N);
-  if (d.prec == kPrecBf16 && ver != 6) return pl;  // bf16 exists on v6 only
+  const GenericU gu = c6 ? GenericU{} : pick_generic_u(d, N, fwd);
+  const int U = c6 ? c6.U : gu.U;
+  if (d.prec == kPrecBf16 && !c6) return pl;  // bf16 exists on v6 only
   if (!U) return pl;
-  pl.ver = ver;
+  pl.ver = c6 ? 6 : 4;
   pl.U = U;
   pl.nwg = d.H / U;
-  if (ver == 6) {
+  if (c6) {
     pl.c6 = c6;
     pl.nth = c6.nth;
     pl.lds = fwd ? fwd6_lds_bytes(d, c6) : bwd6_lds_bytes(d, c6);
@@ -370,12 +352,12 @@ RecPlan plan_rec(const RnnDesc &d, int N, bool fwd) {
     pl.scratch_free = rec6_scratch_free(rec6_kernel(fwd, d.mode, d.prec, d.H, c6));
   } else {
     pl.nth = NT;
-    pl.lds = fwd ? fwd_lds_bytes(d, N, U) : bwd_lds_bytes(d, N, U, ver);
-    pl.xpd = ver == 4 ? v4_xpd(d, U) : 1;
+    pl.lds = fwd ? fwd_lds_bytes(d, N, U) : bwd_lds_bytes(d, N, U);
+    pl.xpd = gu.xpd;
   }
   pl.wgs = d.dirs * pl.nwg * pl.rg;
-  // v4: eight XCD slots of nwg / xpd workgroups; pinned v6: eight of nwg
-  pl.grid = ver == 4 ? 8 * ceil_div(pl.nwg, pl.xpd) : ver == 6 && pl.xpd ? 8 * pl.nwg : pl.wgs;
+  // slot-mapped generic: eight XCD slots of nwg / xpd workgroups; pinned v6: eight of nwg
+  pl.grid = !pl.xpd ? pl.wgs : c6 ? 8 * pl.nwg : 8 * ceil_div(pl.nwg, pl.xpd);
   return pl;
 }
 

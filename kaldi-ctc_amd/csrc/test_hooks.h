@@ -43,11 +43,12 @@ int kctc_test_component_side_streams(struct kctcComponentImpl *h, int on);
  * zeros but the last when v6 does not apply -- and *kernel the address of the
  * kernel the lookup names for it (NULL then).  Nothing is launched. */
 int kctc_test_rec6_select(int mode, int prec, int H, int dirs, int N, int fwd, int cfg[6], const void **kernel);
-/* The whole plan of the recurrence of any version that such a layer runs:
- * plan = {version (6, 4, 3; 0: not supported, then all zeros), U, grid in
+/* The whole plan of the recurrence that such a layer runs: plan = {version (6:
+ * v6, 4: the generic kernels; 0: not supported, then all zeros), U, grid in
  * workgroups, threads per workgroup, dynamic LDS bytes, bit mask of the XCDs
- * a pinned v6 launch occupies, workgroups per (row group, direction), xpd (v4:
- * XCD slots per direction; v6: 1 when pinned)}.  Nothing is launched. */
+ * a pinned v6 launch occupies, workgroups per (row group, direction), xpd
+ * (generic: XCD slots per direction, 0 in plain block mapping; v6: 1 when
+ * pinned)}.  Nothing is launched. */
 int kctc_test_rec_plan(int mode, int prec, int H, int dirs, int N, int fwd, long plan[8]);
 #ifdef __cplusplus
 }

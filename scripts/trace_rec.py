@@ -14,13 +14,13 @@ def main(path):
     tr = np.frombuffer(raw[32:], dtype=np.uint64).reshape(steps, grid, stride or 16).astype(np.int64)
     steps = min(steps, T)
     tr = tr[:steps]
-    if xpd == 0:  # v6: block b -> (dir b % dirs, g b / dirs)
+    if xpd == 0 and ver == 6:  # unpinned v6: block b -> (dir b % dirs, g b / dirs)
         members = [[b for b in range(grid) if b % dirs == d and b // dirs < nwg] for d in range(dirs)]
-    elif ver >= 4:
+    elif xpd == 0:  # generic, plain mapping: block b -> (dir b / nwg, g b % nwg)
+        members = [list(range(d * nwg, (d + 1) * nwg)) for d in range(dirs)]
+    else:  # XCD slots
         members = [[b for b in range(grid) if (b % 8) // xpd == d and (b // 8) * xpd + (b % 8) % xpd < nwg]
                    for d in range(dirs)]
-    else:
-        members = [list(range(d * nwg, (d + 1) * nwg)) for d in range(dirs)]
     active = sorted(b for m in members for b in m)
     tr = tr[:, active, :]
     loc = tr[0, :, 9]

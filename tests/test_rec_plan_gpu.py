@@ -45,9 +45,11 @@ PLANS = [
     ((TANH, X3, 32, 4), (4, 8, 32, 256, 6400, 0, 4, 1), (4, 16, 16, 256, 6400, 0, 2, 1)),
     ((TANH, X3, 256, 16), (4, 8, 256, 256, 20736, 0, 32, 1), (4, 16, 128, 256, 20736, 0, 16, 1)),
     ((LSTM, X3, 384, 16), (4, 16, 192, 256, 115712, 0, 24, 1), (4, 16, 192, 256, 106752, 0, 24, 1)),
-    # v3: no U gives a direction whole XCD slots
-    ((TANH, X3, 1536, 16), (3, 16, 192, 256, 102656, 0, 96, 1), (3, 16, 192, 256, 102656, 0, 96, 1)),
-    ((TANH, X3, 528, 2), (3, 8, 132, 256, 38144, 0, 66, 1), (3, 16, 66, 256, 38144, 0, 33, 1)),
+    # the same kernels in plain block mapping (xpd 0): no U gives a direction whole XCD slots
+    ((TANH, X3, 1536, 16), (4, 16, 192, 256, 102656, 0, 96, 0), (4, 16, 192, 256, 102656, 0, 96, 0)),
+    ((TANH, X3, 528, 2), (4, 8, 132, 256, 38144, 0, 66, 0), (4, 16, 66, 256, 38144, 0, 33, 0)),
+    # ... and no whole-slot U whose backward image (U rows of R^T) fits the LDS
+    ((LSTM, X3, 640, 2), (4, 8, 160, 256, 90624, 0, 80, 0), (4, 8, 160, 256, 86144, 0, 80, 0)),
     # not supported: bf16 exists on v6 only
     ((LSTM, BF16, 384, 16), (0,) * 8, (0,) * 8),
 ]

@@ -66,9 +66,14 @@ CASES = [
     # H = 1024 (configs[4] width)
     (3, 12, 8, 40, 1024, 1, True),   # one group, U=16
     (3, 10, 32, 40, 1024, 1, True),  # 2 groups, U=32 on 512-thread workgroups
-    # v3 (no U gives a direction whole XCD slots): the smallest shape that selects it, the only v3 case
-    # (profiles/r10_parent_rec_plan.txt: the cases above run v4 and v6 kernels only)
+    # generic kernels, plain block mapping (no U gives a direction whole XCD slots): the smallest such shape
     (1, 4, 2, 40, 528, 1, True),
+    (2, 4, 2, 16, 640, 1, True),     # LSTM: the backward's U = 8 rows of R^T under 16-row B fragments
+    (3, 5, 3, 16, 528, 1, True),     # GRU: k-groups no multiple of 4 (the runtime-trip-count step bodies)
+    (1, 4, 20, 16, 528, 1, True),    # two 16-row tiles, the second one ragged
+    # generic kernels, slot mapping: stacked unidirectional RELU, part of one XCD slot (6 workgroups forward,
+    # 3 backward)
+    (0, 6, 4, 12, 48, 2, False),
 ]
 
 

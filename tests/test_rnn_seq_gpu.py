@@ -13,12 +13,13 @@ from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
 
-LSTM, GRU, RELU = 2, 3, 0
+LSTM, GRU, RELU, TANH = 2, 3, 0, 1
 
 CASES = [
     # (id, mode, T, lens, D, H, layers, bidir, prec, env)
     ("v4_lstm", LSTM, 23, [23, 7, 1, 16, 22], 24, 64, 1, True, None, {}),
     ("v3v4_relu", RELU, 15, [15, 4, 9, 1], 12, 32, 1, True, None, {}),
+    ("generic_tanh", TANH, 5, [5, 3, 1], 12, 32, 1, True, None, {}),
     ("v6_gru_one_group", GRU, 21, [21, 20, 13, 5, 1, 21, 9], 64, 256, 1, True, None, {}),
     # row groups of 8 sequences (KCTC_REC_GS=8): 12 sequences are two groups
     ("v6_lstm_two_groups_of_8", LSTM, 18, [18, 1, 7, 12, 3, 18, 9, 2, 17, 5, 11, 14], 40, 512, 1, True, None,
