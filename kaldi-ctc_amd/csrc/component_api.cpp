@@ -9,7 +9,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <fstream>
 #include <memory>
 #include <sstream>
 #include <string>
@@ -20,58 +19,25 @@
 #include "nnet.h"
 #include "nnet_handle.h"
 
-using kctc::nnet2::ChunkInfo;
-using kctc::nnet2::ClipGradientComponent;
-using kctc::nnet2::Component;
-using kctc::nnet2::CuDevice;
-using kctc::nnet2::CuMatrixBase;
-using kctc::nnet2::CuDNNRecurrentComponent;
-using kctc::nnet2::SoftmaxComponent;
-using kctc::nnet2::UpdatableComponent;
+using namespace kctc::nnet2;
 
-struct kctcComponentImpl {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  // test hook (kctc_test_component_side_streams): the trainer's side and
-  // dx-stream queues, so that the component streams and prepacks as in training
-  hipStream_t side = nullptr, stream2 = nullptr;
+// everything of a standalone component on its one stream; side and stream2
+// only from the test hook (kctc_test_component_side_streams): the trainer's
+// side and dx-stream queues, so that it streams and prepacks as in training
+struct kctcComponentImpl : kctcStreams {
   std::unique_ptr<Component> c;
   kctc::GlibcRand rng{0};  // ClipGradient self-repair draws (srand(0))
-  explicit kctcComponentImpl(int dev) : device(dev) {
+  explicit kctcComponentImpl(int dev) {
+    device = dev;
     KCTC_HIP_CHECK(hipSetDevice(dev));
     KCTC_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
   }
-  ~kctcComponentImpl() {
-    if (stream) {
-      (void)hipStreamSynchronize(stream);
-      auto &d = CuDevice::Instantiate();
-      if (d.stream == stream) d.stream = nullptr;
-    }
+  ~kctcComponentImpl() {  // the compute stream outlives the component and goes last
+    quiesce(kCompute);
     c.reset();
-    for (hipStream_t s2 : {side, stream2})
-      if (s2) {
-        (void)hipStreamSynchronize(s2);
-        auto &d = CuDevice::Instantiate();
-        if (d.side == s2) d.side = nullptr;
-        if (d.stream2 == s2) d.stream2 = nullptr;
-        (void)hipStreamDestroy(s2);
-      }
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-  // everything of a standalone component on its one stream (no side streams
-  // unless the test hook gave it the trainer's two)
-  void activate() {
-    KCTC_HIP_CHECK(hipSetDevice(device));
-    auto &d = CuDevice::Instantiate();
-    d.device = device;
-    d.stream = stream;
-    d.side = side;
-    d.stream2 = stream2;
-  }
-  void sync() {
-    for (hipStream_t s2 : {side, stream2})
-      if (s2) KCTC_HIP_CHECK(hipStreamSynchronize(s2));
-    KCTC_HIP_CHECK(hipStreamSynchronize(stream));
+    quiesce(kSide);
+    destroy(kSide);
+    destroy(kCompute);
   }
   UpdatableComponent &u() {
     if (!c->IsUpdatable()) throw std::invalid_argument(c->Type() + " is not an UpdatableComponent");
@@ -80,14 +46,6 @@ struct kctcComponentImpl {
 };
 
 namespace {
-
-std::string slurp(const char *path) {
-  std::ifstream is(path, std::ios::binary);
-  if (!is) throw std::runtime_error(std::string("cannot open ") + path);
-  std::ostringstream ss;
-  ss << is.rdbuf();
-  return ss.str();
-}
 
 // input rows per output frame: the span of Context() (SpliceComponent)
 int num_splice(const Component &c) {
@@ -108,10 +66,6 @@ void chunk_infos(const Component &c, int T, int N, ChunkInfo *in, ChunkInfo *out
   out->first_offset = -c.Context().front();
 }
 
-void set_minibatch(Component &c, int N) {
-  if (auto *r = dynamic_cast<CuDNNRecurrentComponent *>(&c)) r->SetMiniBatch(N);
-}
-
 kctcComponentImpl *wrap(Component *c, int device) {
   std::unique_ptr<Component> own(c);
   auto *h = new kctcComponentImpl(device);
@@ -119,25 +73,10 @@ kctcComponentImpl *wrap(Component *c, int device) {
   return h;
 }
 
-// Scale / Add of the component kinds nnet-am-average touches: UpdatableComponent
-// and the NonlinearComponent statistics (SoftmaxComponent here); ClipGradient
-// counters have the same pair in the reference (nnet-cudnn-component.cc:1064-1073)
-void scale_component(Component &c, float s) {
-  if (c.IsUpdatable()) static_cast<UpdatableComponent &>(c).Scale(s);
-  else if (auto *sm = dynamic_cast<SoftmaxComponent *>(&c)) sm->Scale(s);
-  else if (auto *cg = dynamic_cast<ClipGradientComponent *>(&c)) cg->Scale(s);
-  else throw std::invalid_argument(c.Type() + " has no Scale()");
-}
+// Component::Add between two components of one kind (nnet-am-average)
 void add_component(Component &c, float alpha, const Component &o) {
   if (c.Type() != o.Type()) throw std::invalid_argument("Add: components of different type");
-  if (c.IsUpdatable())
-    static_cast<UpdatableComponent &>(c).Add(alpha, static_cast<const UpdatableComponent &>(o));
-  else if (auto *sm = dynamic_cast<SoftmaxComponent *>(&c))
-    sm->Add(alpha, static_cast<const SoftmaxComponent &>(o));
-  else if (auto *cg = dynamic_cast<ClipGradientComponent *>(&c))
-    cg->Add(alpha, static_cast<const ClipGradientComponent &>(o));
-  else
-    throw std::invalid_argument(c.Type() + " has no Add()");
+  c.Add(alpha, o);
 }
 
 int average_end(const kctc::nnet2::Nnet &n, bool skip_last) {
@@ -153,7 +92,7 @@ bool averaged(const Component &c) { return c.IsUpdatable() || dynamic_cast<const
 void nnet_scale(kctcNnetImpl *n, float s, bool skip_last) {
   const int end = average_end(n->nnet, skip_last);
   for (int c = 0; c < end; c++)
-    if (averaged(n->nnet.GetComponent(c))) scale_component(n->nnet.GetComponent(c), s);
+    if (averaged(n->nnet.GetComponent(c))) n->nnet.GetComponent(c).Scale(s);
 }
 void nnet_add(kctcNnetImpl *n, float alpha, kctcNnetImpl *o, bool skip_last) {
   if (o->nnet.NumComponents() != n->nnet.NumComponents())
@@ -195,7 +134,7 @@ int kctc_component_read(kctcComponent_t *out, const char *path, int device) {
     KCTC_REQUIRE(out && path, "kctc_component_read: null argument");
     std::unique_ptr<kctcComponentImpl> h(new kctcComponentImpl(device));
     h->activate();
-    std::istringstream is(slurp(path));
+    std::istringstream is(kctc::kio::ReadFile(path));
     const bool binary = kctc::kio::InitInput(is);
     h->c.reset(Component::ReadNew(is, binary));
     h->sync();
@@ -207,11 +146,7 @@ int kctc_component_write(kctcComponent_t h, const char *path, int binary) {
   return kctc_guarded([&] {
     KCTC_REQUIRE(h && path, "kctc_component_write: null argument");
     h->activate();
-    std::ofstream os(path, std::ios::binary | std::ios::trunc);
-    if (!os) throw std::runtime_error(std::string("cannot open ") + path);
-    kctc::kio::InitOutput(os, binary != 0);
-    h->c->Write(os, binary != 0);
-    if (!os) throw std::runtime_error(std::string("write failed: ") + path);
+    kctc::kio::WriteFile(path, binary != 0, [&](std::ostream &os) { h->c->Write(os, binary != 0); });
   });
 }
 
@@ -292,7 +227,7 @@ int kctc_component_propagate(kctcComponent_t h, int T, int N, const float *in, l
                  "kctc_component_propagate: in_len != T*N*num_splice*InputDim");
     KCTC_REQUIRE(out_len == rows * c.OutputDim(), "kctc_component_propagate: out_len != T*N*OutputDim");
     h->activate();
-    set_minibatch(c, N);
+    if (auto *r = dynamic_cast<CuDNNRecurrentComponent *>(&c)) r->SetMiniBatch(N);
     ChunkInfo ii, oi;
     chunk_infos(c, T, N, &ii, &oi);
     const CuMatrixBase x(const_cast<float *>(in), rows * num_splice(c), c.InputDim());
@@ -421,7 +356,7 @@ int kctc_component_scale(kctcComponent_t h, float scale) {
   return kctc_guarded([&] {
     KCTC_REQUIRE(h, "null argument");
     h->activate();
-    scale_component(*h->c, scale);
+    h->c->Scale(scale);
     h->sync();
   });
 }

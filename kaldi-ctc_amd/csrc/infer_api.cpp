@@ -1,0 +1,270 @@
+// infer_api.cpp -- C ABI of include/kaldi_ctc_decode.h and the forward-only
+// entry points of kaldi_ctc_train.h: propagate, the CTC decodable (one
+// utterance and batched), posterior sums, priors and compute-prob.
+#include "kaldi_ctc_decode.h"
+
+#include <vector>
+
+#include "decodable.h"
+#include "elementwise.h"
+#include "nnet_handle.h"
+#include "seq_align.h"
+
+using kctc::nnet2::CuDevice;
+
+// the model's priors on the device (nullptr: none), uploaded again only when they change
+static const float *device_priors(kctcNnet_t n, int A) {
+  if (n->priors.empty()) return nullptr;
+  KCTC_REQUIRE((int)n->priors.size() == A, "priors dimension != network output dimension");
+  if (n->dec_priors_host != n->priors) {
+    n->dec_priors.ensure(sizeof(float) * A);
+    KCTC_HIP_CHECK(hipMemcpyAsync(n->dec_priors.p, n->priors.data(), sizeof(float) * A, hipMemcpyHostToDevice,
+                                  n->stream));
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));  // the source is the host vector
+    n->dec_priors_host = n->priors;
+  }
+  return n->dec_priors.f();
+}
+
+// kctc_nnet_profile of the forward-only entry points: their spans are complete
+// after the stream synchronisation (a training step in flight collects its own)
+static void collect_profile(kctcNnet_t n) {
+  if (n->trainer.Pending() == 0 && n->evaluator.Pending() == 0) CuDevice::Instantiate().Collect();
+}
+
+// device-to-device copy of a forward's output into the caller's buffer
+static void copy_out(kctcNnet_t n, const kctc::nnet2::CuMatrixBase &o, float *out_dev, long len, const char *what) {
+  KCTC_REQUIRE(len == o.NumRows() * (long)o.NumCols(), what);
+  KCTC_HIP_CHECK(hipMemcpyAsync(out_dev, o.Data(), sizeof(float) * len, hipMemcpyDeviceToDevice, n->stream));
+  KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+}
+
+// Reads the egs archive and calls fn(batch) for every batch_size examples and
+// for the rest; returns the number of examples.
+template <typename F>
+static long for_each_batch(const char *rspecifier, size_t batch_size, F fn) {
+  kctc::egs::ArchiveReader reader(rspecifier);
+  std::vector<kctc::egs::Example> batch;
+  long ne = 0;
+  kctc::egs::Example eg;
+  while (reader.Next(&eg)) {
+    if (batch.size() == batch_size) {
+      fn(batch);
+      batch.clear();
+    }
+    batch.push_back(std::move(eg));
+    eg = kctc::egs::Example();
+    ne++;
+  }
+  if (!batch.empty()) fn(batch);
+  return ne;
+}
+
+extern "C" {
+
+size_t kctc_ctc_decodable_scratch_bytes(int T) { return kctc::ctc_decodable_scratch_bytes(T > 0 ? T : 1) + 256; }
+
+int kctc_softmax_rows(struct ihipStream_t *stream, const float *in, long rows, int cols, float *out) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(in && out && rows >= 0 && cols > 0, "kctc_softmax_rows: bad argument");
+    kctc::softmax_rows(stream, in, rows, cols, out);
+    KCTC_HIP_CHECK(hipGetLastError());
+  });
+}
+
+int kctc_ctc_decodable(struct ihipStream_t *stream, const float *probs, int T, int A, const float *priors,
+                       float prob_scale, float blank_threshold, float floor_value, float *out, void *scratch,
+                       int *num_kept) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(probs && out && scratch && num_kept && T > 0 && A > 0, "kctc_ctc_decodable: bad argument");
+    int *kept_dev = reinterpret_cast<int *>(static_cast<char *>(scratch) + kctc::ctc_decodable_scratch_bytes(T));
+    kctc::ctc_decodable(stream, probs, T, A, priors, prob_scale, blank_threshold, floor_value, out, scratch,
+                        kept_dev);
+    KCTC_HIP_CHECK(hipGetLastError());
+    KCTC_HIP_CHECK(hipMemcpyAsync(num_kept, kept_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
+    KCTC_HIP_CHECK(hipStreamSynchronize(stream));
+  });
+}
+
+int kctc_nnet_propagate(kctcNnet_t n, const float *feats_dev, int T_max, int N, float *out_dev, long len) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && feats_dev && out_dev, "kctc_nnet_propagate: null argument");
+    n->activate();
+    copy_out(n, n->evaluator.Forward(feats_dev, T_max, N), out_dev, len,
+             "kctc_nnet_propagate: len != T_max*N*output_dim");
+  });
+}
+
+int kctc_am_nnet_decodable(kctcNnet_t n, const float *feats_dev, int T, float prob_scale, float blank_threshold,
+                           float *out_host, int *num_rows) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && feats_dev && out_host && num_rows && T > 0, "kctc_am_nnet_decodable: bad argument");
+    n->activate();
+    // NnetComputation(nnet, feats, pad_input = true) (ctc-decodable-am-nnet.cc:28-52,
+    // nnet-compute.cc:64-90): T output frames from the T feature rows, the
+    // first / last frame repeated LeftContext / RightContext times; a spliced
+    // network reads num_splice rows per output frame (FormatNnetInput layout)
+    const float *in = feats_dev;
+    const int ns = n->nnet.NumSplice();
+    if (ns > 1) {
+      n->dec_input.ensure(sizeof(float) * (size_t)T * ns * n->nnet.InputDim());
+      kctc::pad_splice_input(n->stream, feats_dev, T, n->nnet.InputDim(), n->nnet.LeftContext(), ns,
+                             n->dec_input.f());
+      in = n->dec_input.f();
+    }
+    const auto &o = n->evaluator.Forward(in, T, 1);
+    const int A = o.NumCols();
+    auto &out = n->dec_out, &scratch = n->dec_scratch;
+    const float *pd = device_priors(n, A);
+    out.ensure(sizeof(float) * (size_t)T * A);
+    scratch.ensure(kctc_ctc_decodable_scratch_bytes(T));
+    int kept = 0;
+    const int st = kctc_ctc_decodable(n->stream, o.Data(), T, A, pd, prob_scale, blank_threshold, 1.0e-10f, out.f(),
+                                      scratch.p, &kept);
+    if (st) throw std::runtime_error(kctc_last_error());
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+    KCTC_HIP_CHECK(hipMemcpy(out_host, out.p, sizeof(float) * (size_t)kept * A, hipMemcpyDeviceToHost));
+    *num_rows = kept;
+  });
+}
+
+int kctc_nnet_propagate_seq(kctcNnet_t n, const float *feats_dev, int T_max, int N, const int *num_frames,
+                            float *out_dev, long len) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && feats_dev && out_dev && num_frames, "kctc_nnet_propagate_seq: null argument");
+    n->activate();
+    copy_out(n, n->evaluator.ForwardSeq(feats_dev, T_max, N, num_frames), out_dev, len,
+             "kctc_nnet_propagate_seq: len != T_max*N*output_dim");
+    collect_profile(n);
+  });
+}
+
+int kctc_am_nnet_decodable_batch(kctcNnet_t n, const float *feats_dev, int T_max, int N, const int *num_frames,
+                                 float prob_scale, float blank_threshold, float *out_host, int *rows) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && feats_dev && num_frames && out_host && rows && T_max > 0 && N > 0,
+                 "kctc_am_nnet_decodable_batch: bad argument");
+    long total = 0;
+    for (int u = 0; u < N; u++) {
+      KCTC_REQUIRE(num_frames[u] >= 1 && num_frames[u] <= T_max,
+                   "kctc_am_nnet_decodable_batch: num_frames outside [1, T_max]");
+      total += num_frames[u];
+    }
+    n->activate();
+    const int D = n->nnet.InputDim();
+    if (n->nnet.NumSplice() > 1) {
+      // a network with frame context pads every utterance at its own ends
+      // (pad_input = true): one utterance at a time through kctc_am_nnet_decodable
+      long off = 0;
+      for (int u = 0; u < N; u++) {
+        const int T = num_frames[u];
+        n->dec_gather.ensure(sizeof(float) * (size_t)T * D);
+        KCTC_HIP_CHECK(hipMemcpy2DAsync(n->dec_gather.p, sizeof(float) * D, feats_dev + (size_t)u * D,
+                                        sizeof(float) * (size_t)N * D, sizeof(float) * D, T,
+                                        hipMemcpyDeviceToDevice, n->stream));
+        const int A = n->nnet.OutputDim();
+        if (kctc_am_nnet_decodable(n, n->dec_gather.f(), T, prob_scale, blank_threshold, out_host + off * A,
+                                   &rows[u]))
+          throw std::runtime_error(kctc_last_error());
+        off += rows[u];
+      }
+      return;
+    }
+    kctc::SeqLens lens;
+    KCTC_REQUIRE(kctc::seq_lens(num_frames, T_max, N, &lens), "kctc_am_nnet_decodable_batch: more than 64 utterances");
+    const auto &o = n->evaluator.ForwardSeq(feats_dev, T_max, N, num_frames);
+    const int A = o.NumCols();
+    const float *pd = device_priors(n, A);
+    n->dec_out.ensure(sizeof(float) * (size_t)total * A);
+    n->dec_scratch.ensure(kctc::seq_decodable_scratch_bytes(T_max, N));
+    n->dec_kept.ensure(sizeof(int) * kctc::kSeqMaxN);
+    int *kept_dev = static_cast<int *>(n->dec_kept.p);
+    kctc::seq_decodable(n->stream, o.Data(), T_max, N, A, lens, pd, prob_scale, blank_threshold, 1.0e-10f,
+                        n->dec_out.f(), n->dec_scratch.p, kept_dev);
+    KCTC_HIP_CHECK(hipMemcpyAsync(rows, kept_dev, sizeof(int) * N, hipMemcpyDeviceToHost, n->stream));
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+    collect_profile(n);
+    long kept = 0;
+    for (int u = 0; u < N; u++) kept += rows[u];
+    KCTC_REQUIRE(kept <= total, "kctc_am_nnet_decodable_batch: kept more rows than frames");
+    KCTC_HIP_CHECK(hipMemcpy(out_host, n->dec_out.p, sizeof(float) * (size_t)kept * A, hipMemcpyDeviceToHost));
+  });
+}
+
+int kctc_nnet_sum_posteriors(kctcNnet_t n, const char *rspecifier, int minibatch_size, double *sum, int A,
+                             long *frames, long *num_egs) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && rspecifier && sum, "kctc_nnet_sum_posteriors: null argument");
+    KCTC_REQUIRE(minibatch_size >= 1 && minibatch_size <= kctc::kSeqMaxN,
+                 "kctc_nnet_sum_posteriors: minibatch_size outside [1, 64]");
+    KCTC_REQUIRE(A == n->nnet.OutputDim(), "kctc_nnet_sum_posteriors: A != network output dimension");
+    n->activate();
+    n->post_sum.ensure(sizeof(double) * A);
+    KCTC_HIP_CHECK(hipMemsetAsync(n->post_sum.p, 0, sizeof(double) * A, n->stream));
+    long nf = 0;
+    const long ne = for_each_batch(rspecifier, minibatch_size, [&](std::vector<kctc::egs::Example> &batch) {
+      // every example from its own start offset (eg.left_context - nnet.LeftContext()), pad_input = false
+      std::unique_ptr<kctc::egs::Minibatch> mb =
+          kctc::egs::pack_minibatch(batch, n->nnet.LeftContext(), n->nnet.RightContext(), true);
+      n->check_input_dim(*mb);
+      kctc::SeqLens lens;
+      if (!kctc::seq_lens(mb->num_frames.data(), mb->T_max, mb->N, &lens))
+        throw std::invalid_argument("an example is shorter than the network's context");
+      n->stage_minibatch(*mb);
+      const auto &o = n->evaluator.ForwardSeq(n->egs_feats.f(), mb->T_max, mb->N, mb->num_frames.data());
+      n->post_scratch.ensure(kctc::seq_post_sum_scratch_bytes(mb->T_max, mb->N, A));
+      kctc::seq_post_sum(n->stream, o.Data(), mb->T_max, mb->N, A, lens, static_cast<double *>(n->post_sum.p),
+                         n->post_scratch.p);
+      for (int f : mb->num_frames) nf += f;
+    });
+    KCTC_HIP_CHECK(hipMemcpyAsync(sum, n->post_sum.p, sizeof(double) * A, hipMemcpyDeviceToHost, n->stream));
+    KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+    collect_profile(n);
+    if (frames) *frames = nf;
+    if (num_egs) *num_egs = ne;
+  });
+}
+
+int kctc_am_nnet_adjust_priors(kctcNnet_t n, const double *posterior_sum, int A, float google_prior_const) {
+  return kctc_guarded([&] {  // nnet-adjust-priors.cc:126-140
+    KCTC_REQUIRE(n, "kctc_am_nnet_adjust_priors: null argument");
+    KCTC_REQUIRE(A == n->nnet.OutputDim(), "kctc_am_nnet_adjust_priors: A != number of pdfs");
+    std::vector<float> p((size_t)A, 1.0f);
+    if (google_prior_const != 0.f) {
+      p[0] = google_prior_const;  // un-normalised, as the reference leaves it
+    } else {
+      KCTC_REQUIRE(posterior_sum, "kctc_am_nnet_adjust_priors: null posterior sum");
+      double tot = 0.0;
+      for (int a = 0; a < A; a++) tot += posterior_sum[a];
+      KCTC_REQUIRE(tot > 0.0, "kctc_am_nnet_adjust_priors: the posterior sum must be positive");
+      for (int a = 0; a < A; a++) p[a] = (float)(posterior_sum[a] / tot);
+    }
+    n->priors = p;
+  });
+}
+
+int kctc_nnet_compute_prob(kctcNnet_t n, const char *rspecifier, long *num_examples, double *tot_like,
+                           double *tot_accuracy, double *tot_weight) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && rspecifier, "kctc_nnet_compute_prob: null argument");
+    n->activate();
+    double like = 0, acc = 0, w = 0;
+    // ComputeNnetObjf on batches of 10 (ctc-nnet-update.cc:426-431)
+    const long ne = for_each_batch(rspecifier, 10, [&](std::vector<kctc::egs::Example> &batch) {
+      std::unique_ptr<kctc::egs::Minibatch> mb =
+          kctc::egs::pack_minibatch(batch, n->nnet.LeftContext(), n->nnet.RightContext());
+      n->stage_minibatch(*mb);
+      const auto st = n->evaluator.ComputeForMinibatch(n->egs_feats.f(), mb->T_max, mb->N, mb->num_frames.data(),
+                                                       mb->labels.data(), mb->label_lengths.data());
+      like += st.tot_objf;
+      acc += st.tot_accuracy;
+      w += st.tot_weight;  // TotalNnetTrainingWeight: sum of label counts
+    });
+    if (num_examples) *num_examples = ne;
+    if (tot_like) *tot_like = like;
+    if (tot_accuracy) *tot_accuracy = acc;
+    if (tot_weight) *tot_weight = w;
+  });
+}
+
+}  // extern "C"

@@ -14,10 +14,12 @@
 #include <cctype>
 #include <cstdint>
 #include <cstring>
+#include <fstream>
 #include <iomanip>
 #include <istream>
 #include <limits>
 #include <ostream>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -42,6 +44,24 @@ inline bool InitInput(std::istream &is) {
     return true;
   }
   return false;
+}
+
+// a whole file in memory (models are ~0.1 GB)
+inline std::string ReadFile(const char *path) {
+  std::ifstream is(path, std::ios::binary);
+  if (!is) throw std::runtime_error(std::string("cannot open ") + path);
+  std::ostringstream ss;
+  ss << is.rdbuf();
+  return ss.str();
+}
+// opens `path`, writes the mode header, runs body(os) and checks the stream
+template <typename F>
+void WriteFile(const char *path, bool binary, F body) {
+  std::ofstream os(path, std::ios::binary | std::ios::trunc);
+  if (!os) throw std::runtime_error(std::string("cannot open ") + path);
+  InitOutput(os, binary);
+  body(os);
+  if (!os) throw std::runtime_error(std::string("write failed: ") + path);
 }
 
 inline void WriteToken(std::ostream &os, bool, const std::string &t) {

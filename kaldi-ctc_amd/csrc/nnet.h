@@ -155,6 +155,11 @@ class Component {
   // copied CuDNNRecurrentComponent must Propagate before it can Backprop
   virtual Component *Copy() const = 0;
   virtual void ZeroStats() {}
+  // nnet-am-average's pair, for the kinds it touches (parameters, the
+  // NonlinearComponent statistics, the ClipGradient counters); `other` is of
+  // this component's Type().  The rest throw.
+  virtual void Scale(float scale);
+  virtual void Add(float alpha, const Component &other);
   // frame offsets this component reads relative to each output frame
   // (nnet-component.h:188; only SpliceComponent has more than {0})
   virtual std::vector<int> Context() const { return std::vector<int>(1, 0); }
@@ -182,8 +187,8 @@ class UpdatableComponent : public Component {
   // params += stddev * N(0,1), from the process's perturbation stream
   // (SetPerturbSeed; each call draws fresh noise)
   virtual void PerturbParams(float stddev);
-  virtual void Scale(float scale);
-  virtual void Add(float alpha, const UpdatableComponent &other);
+  void Scale(float scale) override;
+  void Add(float alpha, const Component &other) override;
   bool IsGradient() const { return is_gradient_; }
   static void SetPerturbSeed(unsigned long long seed);
   virtual long NumParameters() const = 0;
@@ -376,8 +381,8 @@ class ClipGradientComponent : public Component {
   Component *Copy() const override;
   void ZeroStats() override;
   // the counters' Scale / Add (nnet-cudnn-component.cc:1064-1073)
-  void Scale(float scale);
-  void Add(float alpha, const ClipGradientComponent &other);
+  void Scale(float scale) override;
+  void Add(float alpha, const Component &other) override;
   // host view of the device counters (valid after a stream sync)
   void SyncStats() const;
   double NumClipped() const { return num_clipped_; }
@@ -472,8 +477,8 @@ class SoftmaxComponent : public Component {
   void Read(std::istream &is, bool binary) override;
   Component *Copy() const override;
   // NonlinearComponent::Scale / Add of the statistics (nnet-am-average)
-  void Scale(float scale);
-  void Add(float alpha, const SoftmaxComponent &other);
+  void Scale(float scale) override;
+  void Add(float alpha, const Component &other) override;
   const std::vector<double> &ValueSum() const { return value_sum_; }
   double Count() const { return count_; }
 
@@ -539,6 +544,7 @@ class Nnet {
   int InputDim() const { return components_.front()->InputDim(); }
   int OutputDim() const { return components_.back()->OutputDim(); }
   void ZeroStats();
+  void SetMiniBatch(int N);  // every CuDNNRecurrentComponent's (nnet-nnet.cc:42-50)
   void SetLearningRate(float lr);
   void SetMomentum(float m);
   float Momentum() const { return momentum_; }
@@ -558,7 +564,7 @@ class Nnet {
   float momentum_ = 0.f;
 };
 
-// Data-parallel gradient exchange (RCCL over xGMI); implemented in dp.cpp.
+// Data-parallel gradient exchange (RCCL over xGMI); implemented in grad_exchange.cpp.
 class GradExchange {
  public:
   virtual ~GradExchange() = default;
@@ -579,7 +585,7 @@ struct MinibatchStats {
   double tot_objf = 0, tot_accuracy = 0, tot_weight = 0;
 };
 
-// kaldi::LevenshteinEditDistance (unit costs), bit-parallel (nnet.cpp)
+// kaldi::LevenshteinEditDistance (unit costs), bit-parallel (ctc_updater.cpp)
 int levenshtein(const int *ref, int m, const int *hyp, int n);
 
 class NnetCtcUpdater {
@@ -627,6 +633,10 @@ class NnetCtcUpdater {
   void ComponentsChanged();
 
  private:
+  // what every minibatch starts with: the shape check, the RNNs' minibatch
+  // size and (cleared) error word, the chunk infos and the input view
+  void BeginStep(const float *feats, int T_max, int N);
+  void ThrowIfErrWord();  // synchronous read-back of the step's error word
   void SetupChunks(int T_max, int N);
   void Propagate(int T, int N);
   void Backprop(int T, int N);

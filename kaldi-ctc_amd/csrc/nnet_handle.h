@@ -1,5 +1,6 @@
 // nnet_handle.h -- the object behind the kctcNnet_t handle of
-// include/kaldi_ctc_train.h (shared by train_api.cpp and component_api.cpp).
+// include/kaldi_ctc_train.h and what the C-ABI sources share: the streams a
+// handle owns and the exception mapper.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,19 +8,53 @@
 #include <vector>
 
 #include "common.h"
+#include "egs.h"
 #include "kaldi_ctc_train.h"
 #include "nnet.h"
 
-struct kctcNnetImpl {
+// The streams of a network or standalone-component handle.  The owner's
+// destructor calls quiesce / destroy in the order its other members need.
+struct kctcStreams {
+  enum { kCompute = 1, kSide = 2, kAll = 3 };
   int device = 0;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr, side = nullptr, stream2 = nullptr;
+  // this handle's device and streams become the calling thread's CuDevice
+  void activate() {
+    KCTC_HIP_CHECK(hipSetDevice(device));
+    auto &d = kctc::nnet2::CuDevice::Instantiate();
+    d.device = device;
+    d.stream = stream;
+    d.side = side;
+    d.stream2 = stream2;
+  }
+  void sync() {
+    for (hipStream_t s : {side, stream2, stream})
+      if (s) KCTC_HIP_CHECK(hipStreamSynchronize(s));
+  }
+  // waits for the streams of `part` and takes them out of the thread's CuDevice
+  void quiesce(int part) {
+    auto &d = kctc::nnet2::CuDevice::Instantiate();
+    if ((part & kCompute) && stream) (void)hipStreamSynchronize(stream);
+    if ((part & kSide) && side) (void)hipStreamSynchronize(side);
+    if ((part & kSide) && stream2) (void)hipStreamSynchronize(stream2);
+    if ((part & kCompute) && d.stream == stream) d.stream = nullptr;
+    if ((part & kSide) && d.side == side) d.side = nullptr;
+    if ((part & kSide) && d.stream2 == stream2) d.stream2 = nullptr;
+  }
+  void destroy(int part) {
+    if ((part & kCompute) && stream) (void)hipStreamDestroy(stream);
+    if ((part & kSide) && side) (void)hipStreamDestroy(side);
+    if ((part & kSide) && stream2) (void)hipStreamDestroy(stream2);
+  }
+};
+
+struct kctcNnetImpl : kctcStreams {
   kctc::nnet2::Nnet nnet;
   kctc::nnet2::NnetCtcUpdater trainer{&nnet, true};
   kctc::nnet2::NnetCtcUpdater evaluator{&nnet, false};
-  hipStream_t side = nullptr, stream2 = nullptr;
   kctc::nnet2::GradExchange *dp = nullptr;
   bool dp_average = false;  // model averaging: no per-step gradient exchange
-  kctc::nnet2::DevBuf egs_feats, egs_scratch;  // TrainNnetSimple staging
+  kctc::nnet2::DevBuf egs_feats, egs_scratch;  // stage_minibatch
   // decodable (per utterance): device priors, uploaded again only when they
   // change, and the output / scratch buffers, grown and kept
   kctc::nnet2::DevBuf dec_priors, dec_out, dec_scratch, dec_input;
@@ -35,31 +70,23 @@ struct kctcNnetImpl {
   std::vector<float> priors;
   ~kctcNnetImpl() {
     delete dp;
-    if (stream) (void)hipStreamSynchronize(stream);
-    if (side) (void)hipStreamSynchronize(side);
-    if (stream2) (void)hipStreamSynchronize(stream2);
-    auto &d = kctc::nnet2::CuDevice::Instantiate();
-    if (d.stream == stream) d.stream = nullptr;
-    if (d.side == side) d.side = nullptr;
-    if (d.stream2 == stream2) d.stream2 = nullptr;
-    if (stream) (void)hipStreamDestroy(stream);
-    if (side) (void)hipStreamDestroy(side);
-    if (stream2) (void)hipStreamDestroy(stream2);
+    quiesce(kAll);
+    destroy(kAll);
   }
   // compute stream at the highest priority (the latency-bound recurrences),
-  // the weight-gradient side stream at the lowest (train_api.cpp)
+  // the weight-gradient side stream at the lowest (nnet_api.cpp)
   void create_streams();
-  void activate() {
-    KCTC_HIP_CHECK(hipSetDevice(device));
-    auto &d = kctc::nnet2::CuDevice::Instantiate();
-    d.device = device;
-    d.stream = stream;
-    d.side = side;
-    d.stream2 = stream2;
-  }
+  // an egs minibatch formatted into egs_feats on the compute stream, after
+  // the check that its input dimension is the network's (train_api.cpp); a
+  // caller with checks of its own between the two makes that one first
+  void check_input_dim(const kctc::egs::Minibatch &mb) const;
+  void stage_minibatch(kctc::egs::Minibatch &mb);
 };
 
-// kctc_last_error() text of the calling thread (train_api.cpp)
+// CUs this process may use when ranks share a device, 0: all (nnet_api.cpp)
+int kctc_usable_cus_override();
+
+// kctc_last_error() text of the calling thread (nnet_api.cpp)
 void kctc_set_error(const char *msg);
 
 // runs f, mapping exceptions to a non-zero return and kctc_last_error()

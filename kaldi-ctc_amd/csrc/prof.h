@@ -1,5 +1,5 @@
 // prof.h -- optional per-kernel timing with hipEvents on the launch stream
-// (implemented by CuDevice in nnet.cpp; no-ops unless profiling is enabled).
+// (implemented by CuDevice in cu_device.cpp; no-ops unless profiling is enabled).
 #pragma once
 #include <hip/hip_runtime.h>
 

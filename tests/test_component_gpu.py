@@ -408,7 +408,7 @@ def test_forward_prepacks_not_reused_when_stale(kctc, gpu, case):
     """The forward packs W^T (for the streamed dx) and x^T / y^T (for the
     weight GEMMs) beside its recurrence; Backprop reuses them only while the
     parameters are the ones packed (a parameter-version counter) and the
-    in / out buffers are the ones propagated (nnet.cpp wgrad_prepack).
+    in / out buffers are the ones propagated (rnn_component.cpp wgrad_prepack).
     params_written: Propagate, then UnVectorize new parameters, then Backprop
     -- dx and the gradient must be those of the new parameters (a reused W^T
     would give the old ones'); other_buffers: Backprop given copies of the

@@ -1,5 +1,5 @@
 """Data-parallel semantics on CPU (world_size 2, gloo) -- the host logic of the
-RCCL path (train_api.cpp RcclExchange): each rank back-propagates its own
+RCCL path (grad_exchange.cpp RcclExchange): each rank back-propagates its own
 utterance shard, the weight gradients are SUM-all-reduced, then the reference's
 per-component update (RNN dW clipped to +-clip-gradient, W += lr * dW) runs on
 every rank.  Checked against the fp64 oracle on the concatenated minibatch:

@@ -1,4 +1,4 @@
-"""DropoutComponent on the GPU (csrc/dropout.hip, csrc/nnet.cpp): the mask is
+"""DropoutComponent on the GPU (csrc/dropout.hip, csrc/components.cpp): the mask is
 the documented one (kaldi_ctc_amd.dropout_mask, a numpy restatement of
 csrc/dropout.h) bit for bit, forward and backward; its statistics; the
 reference's file format; and the trainer with DropoutComponents between every
