@@ -6,6 +6,21 @@
 
 namespace kctc {
 
+// The producer side of a launch streamed off a running v6 recurrence (filled
+// by rnn_stream.hip stream_producer; lines null: not a streamed launch)
+struct StreamProducer {
+  const unsigned *lines = nullptr;  // its epoch lines: word 32 * (d * nwg + g) holds the WG's epoch = step + 2
+  int nwg = 0;                      // lines per (row group, direction): one when pinned (aggregated)
+  // XCD-pinned producer (rnn_plan.hip xcd_mask): its workgroups OR 1 << XCC_ID
+  // into *xcd_word as they start; a block waits until xcd_count XCDs are
+  // registered and exits before taking work if it is on one of them
+  const unsigned *xcd_word = nullptr;
+  int xcd_count = 0;
+  // persistent blocks (each takes a CU), scaled so that the budget stays
+  // beside the blocks that leave the pinned XCDs
+  int blocks = 0;
+};
+
 // Split-fp16 GEMM on packed operands (x3p_gemm.hip).  Packed operand:
 // [rows][KB][64] fp16 = per 32-k block 32 hi then 32 lo halves of the row
 // scaled by 2^e[row]; e[] int per row.  C[b][m][n] = alpha 2^-(eA[m]+eB[n])
@@ -25,16 +40,16 @@ struct X3PArgs {
   int max_blocks = 0;
   int *tile_counter = nullptr;
   int eA0 = 0, eB0 = 0;  // exponents used when eA / eB is null
-  // Streaming mode (stream_flags != null): the A rows are frames (t, n),
+  // Streaming mode (producer.lines != null): the A rows are frames (t, n),
   // row = t * stream_N + n, produced by a concurrently running bidirectional
   // v6 forward recurrence; a row tile is computed only once direction 0 has
-  // published step t_max of the tile and direction 1 step T-1-t_min (flag
-  // lines of rnn.hip: word 32 * (d * nwg + g) holds the WG's epoch = step + 2).
+  // published step t_max of the tile and direction 1 step T-1-t_min.
   // A is the producer's exchange-image array, read in place with sc1 loads
   // (eA0 = 14, KB over both directions).  Row tiles are taken in readiness order.
-  // tile_counter is required; the grid must leave >= 64 CUs to the producer.
-  const unsigned *stream_flags = nullptr;
-  int stream_nwg = 0, stream_T = 0, stream_N = 0;
+  // tile_counter is required; producer.blocks (not max_blocks) bounds the
+  // grid, which must leave >= 64 CUs to the producer.
+  StreamProducer producer;
+  int stream_T = 0, stream_N = 0;
   long stream_step = 0;              // halves per producer step image (A = image of step 0)
   int stream_rg = 1;                  // producer row groups (N > 16): flags and image parts per group
   int stream_gs = 16;                 // sequences per producer row group (16 or 8)
@@ -44,10 +59,6 @@ struct X3PArgs {
   float *stream_part = nullptr;         // [row tiles][batch][col tiles][128 x 128] half-K partials
   long stream_group_step = 0;         // halves per row group's part of a step image
   unsigned *stream_err = nullptr;    // set (bit 2) if the producer stops publishing
-  // XCD-pinned producer (rnn_plan.hip xcd_mask): blocks on its XCDs exit before
-  // taking work, as in X3PBwdStream
-  const unsigned *stream_xcd_word = nullptr;
-  int stream_xcd_count = 0;
   // bf16 operands (bf16_pack_rows / _cols: [rows][KB][64] bf16, KB = 64-k
   // blocks, no exponents): two v_mfma_f32_16x16x32_bf16 per stage, fp32
   // accumulation; streaming: A = a bf16 v6 forward's h images (eA0 = 0)
@@ -82,8 +93,7 @@ float x3p_bench(hipStream_t s, int M, int N, int K, bool bf16, int iters, int sp
 // ceil(K / 64)) and columns (the transpose, source row k - shift), zero pad
 void bf16_pack_rows(hipStream_t s, const float *X, long ldx, int R, int K, __bf16 *out, int batch = 1, long sX = 0,
                     long sOut = 0);
-void bf16_pack_cols(hipStream_t s, const float *X, long ldx, int R, int Cn, int shift, __bf16 *out, int batch = 1,
-                    long sX = 0, long sOut = 0);
+void bf16_pack_cols(hipStream_t s, const float *X, long ldx, int R, int Cn, int shift, __bf16 *out);
 
 // C = sum over the two directions d of A_d B_d^T, where A_d = columns
 // [d * edoff, d * edoff + 32 KB) of the rows of E, produced step by step by a
@@ -105,17 +115,11 @@ struct X3PBwdStream {
   long ldc = 0;
   float *part = nullptr;               // x3p_bwd_stream_part_floats(M, N) floats
   int *cnt = nullptr;                  // x3p_bwd_stream_ints(M, N) ints (zeroed here)
-  const unsigned *flags = nullptr;     // producer flag lines
-  int nwg = 0, T = 0, Nf = 0;
+  StreamProducer producer;             // flag lines, pinned XCDs, persistent blocks (96 KB LDS each)
+  int T = 0, Nf = 0;
   int rg = 1;                          // producer row groups of 16 sequences
   unsigned *err = nullptr;
-  int blocks = 0;                      // persistent blocks (each takes a CU: 96 KB LDS)
   bool bf16 = false;                   // rows packed as bf16 ([M][KB][64], KB 64-k blocks), B bf16, no exponents
-  // XCD-pinned producer (rnn_plan.hip xcd_mask): its workgroups OR
-  // 1 << XCC_ID into *xcd_word as they start; a block waits until
-  // xcd_count XCDs are registered and exits if it is on one of them
-  const unsigned *xcd_word = nullptr;
-  int xcd_count = 0;
   // FORWARD producer (the next component's input projection streamed off a
   // v6 forward's y rows, written through with the same epochs): direction 0
   // walks the frames upwards, 1 downwards; C += bias + bias2 of column c at
@@ -150,12 +154,17 @@ void x3p_pack_rows(hipStream_t s, const float *X, long ldx, int R, int K, _Float
                    int batch = 1, long sX = 0, long sOut = 0, long sE = 0);
 // pack the transpose: packed row c < Cn = column c of X over its R rows
 // (source row k - shift at k, zero outside), exponents from cmax[c] (float
-// bits of max |x| of the column) or the bound
+// bits of max |x| of the column) or the bound.  Beside a pinned recurrence
+// (PackAvoid::word: X3PArgs::avoid_word, of nxcd XCDs) the blocks on its XCDs
+// leave and the others take item runs from `counter`, a zeroed int
+struct PackAvoid {
+  const unsigned *word = nullptr;
+  int nxcd = 8;
+  int *counter = nullptr;
+  PackAvoid at(int i) const { return {word, nxcd, counter + i}; }  // the i-th counter after this one
+};
 void x3p_pack_cols(hipStream_t s, const float *X, long ldx, int R, int Cn, int shift, _Float16 *out, int *eout,
-                   const unsigned *cmax, float bound, int batch = 1, long sX = 0, long sOut = 0, long sE = 0,
-                   long sCm = 0,
-                   // avoid: X3PArgs::avoid_word; then counter: a zeroed int (dynamic item runs)
-                   const unsigned *avoid = nullptr, int nxcd = 8, int *counter = nullptr);
+                   const unsigned *cmax, float bound, PackAvoid avoid = {});
 inline size_t x3p_bytes(long rows, long K) { return (size_t)rows * ((K + 31) / 32) * 64 * 2; }
 
 }  // namespace kctc

@@ -8,7 +8,7 @@
 //                                       SetZero / DotProduct / PerturbParams /
 //                                       Scale / Add
 //   SpliceComponent                     any sorted context, const-component-dim
-//   CuDNNRecurrentComponent             -> rnn.hip (cuDNN-shaped gfx950 kernels)
+//   CuDNNRecurrentComponent             -> rnn.h (cuDNN-shaped gfx950 layer; host units: rnn.hip)
 //   ClipGradientComponent               -> elementwise.hip / clipgrad.hip
 //   AffineComponent                     -> gemm.hip
 //   DropoutComponent                    -> dropout.hip (regenerated Philox mask)

@@ -1,4 +1,4 @@
-// rec_gate.h -- what rnn.hip needs from the residency machinery of
+// rec_gate.h -- what the RNN host (rnn_host.h) needs from the residency machinery of
 // rec_gate.hip (private to csrc/; the public part is in rnn.h).
 #pragma once
 #include "rec_common.h"

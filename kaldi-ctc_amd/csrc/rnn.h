@@ -102,13 +102,13 @@ void rnn_comm_gate(hipStream_t s, unsigned long long target);
 void rnn_resident_gate(hipStream_t s, const unsigned *flags, unsigned target);
 // Launches beside a running recurrence.  Every v6 recurrence counts its
 // resident workgroups in its own flag area (kResWord, zeroed with the flags
-// before the launch).  Each kernel that rnn.hip puts on another stream while
+// before the launch).  Each kernel that the RNN host puts on another stream while
 // that recurrence runs -- the streamed GEMMs, the wgrad chunk gates, the
 // forward-time packs -- is enqueued behind a gate kernel waiting for that count
 // (rec_gate.hip beside_recurrence): nothing there can take a CU before every
 // workgroup of the recurrence holds its own, so a consumer spinning on the
 // recurrence's progress cannot keep a producer workgroup out.  The host
-// refuses a streaming launch (gemm_x3p with stream_flags,
+// refuses a streaming launch (gemm_x3p with producer.lines,
 // gemm_x3p_bwd_stream) on a stream that has not passed the gate of the
 // recurrence this thread has in flight: rnn_side_gated(s) is false then.
 bool rnn_side_gated(hipStream_t s);
@@ -167,10 +167,15 @@ struct RnnPrepack {
   float in_bound = 0.f;  // |x| <= in_bound (> 0 required)
   bool wdone = false;
 };
+struct RnnFwdOpts {
+  RnnFwdChain *chain = nullptr;
+  bool input_projected = false;   // layer 0's projection is in the reserve (the previous component's chain)
+  const void *in_rows = nullptr;
+  RnnPrepack *pre = nullptr;
+};
 int rnn_forward_training(const RnnDesc &d, hipStream_t s, int T, int N, const float *x,
                          const float *w, float *y, void *workspace, size_t ws_bytes,
-                         void *reserve, size_t res_bytes, unsigned *err, RnnFwdChain *chain = nullptr,
-                         bool input_projected = false, const void *in_rows = nullptr, RnnPrepack *pre = nullptr);
+                         void *reserve, size_t res_bytes, unsigned *err, const RnnFwdOpts &o = {});
 // Length-aware inference: N sequences of host lengths seq_lengths[n] in
 // [1, T] (read before the call returns; KRNN_BAD_PARAM otherwise) run as one
 // batch, each with the result it would get alone with hx = cx = 0:
@@ -217,16 +222,18 @@ int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float
                       hipStream_t overlap = nullptr,  // overlap: stream for the streamed dx GEMM
                       RnnWgradStream *wgrad = nullptr,
                       const RnnPrepack *pre = nullptr);  // W^T packed by the forward (done)
+struct RnnWgradOpts {
+  int max_blocks = 0;             // > 0: persistent weight GEMMs of at most this many blocks
+  float in_bound = 0.f;           // > 0: |x| <= in_bound (an LSTM/GRU below)
+  hipStream_t s2 = nullptr;       // second stream: dW beside dR (nothing else to overlap)
+  const void *in_cols = nullptr;  // bf16: x packed as columns (rnn_packed_output)
+  // runs beside another component's backward recurrence (the side stream): dW
+  // and dR as one launch, kept off the XCDs pinned recurrences run on
+  bool beside = false;
+  const RnnPrepack *pre = nullptr;  // wdone: x^T / y^T packed by the forward
+};
 int rnn_backward_weights(const RnnDesc &d, hipStream_t s, int T, int N, const float *x,
                          const float *y, void *workspace, size_t ws_bytes, float *dw,
-                         void *reserve, size_t res_bytes, int max_blocks = 0,
-                         float in_bound = 0.f,  // > 0: |x| <= in_bound (an LSTM/GRU below)
-                         hipStream_t s2 = nullptr,  // second stream: dW beside dR (nothing else to overlap)
-                         const void *in_cols = nullptr,  // bf16: x packed as columns (rnn_packed_output)
-                         // runs beside another component's backward recurrence
-                         // (the side stream): dW and dR as one launch, kept
-                         // off the XCDs pinned recurrences run on
-                         bool beside = false,
-                         const RnnPrepack *pre = nullptr);  // wdone: x^T / y^T packed by the forward
+                         void *reserve, size_t res_bytes, const RnnWgradOpts &o = {});
 
 }  // namespace kctc

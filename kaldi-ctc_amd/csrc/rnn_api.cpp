@@ -1,4 +1,4 @@
-// rnn_api.cpp -- C ABI of include/kaldi_rnn.h over the gfx950 RNN layer (rnn.hip).
+// rnn_api.cpp -- C ABI of include/kaldi_rnn.h over the gfx950 RNN layer (rnn.h; host units: rnn.hip).
 #include "kaldi_rnn.h"
 
 #include <hip/hip_runtime.h>

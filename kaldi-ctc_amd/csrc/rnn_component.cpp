@@ -132,9 +132,10 @@ void CuDNNRecurrentComponent::Forward(const CuMatrixBase &in, CuMatrixBase *out,
   pre_.done = pre_.wdone = false;
   pre_x_ = in.Data();
   pre_y_ = out->Data();
+  RnnFwdOpts o;
+  o.chain = chain; o.input_projected = projected; o.in_rows = in_rows_; o.pre = pre;
   int st = rnn_forward_training(desc_, S(), T, N, in.Data(), params_.f(), out->Data(), workspace_.p,
-                                workspace_.bytes, reserve_.p, reserve_.bytes, DeviceError(), chain, projected, in_rows_,
-                                pre);
+                                workspace_.bytes, reserve_.p, reserve_.bytes, DeviceError(), o);
   pre_ver_ = pver_;
   if (st) throw std::runtime_error("rnn_forward_training failed: " + std::to_string(st));
 }
@@ -192,10 +193,11 @@ void CuDNNRecurrentComponent::Backprop(const ChunkInfo &, const ChunkInfo &,
     if (!wg.done) {
       dev0.Fork();
       ProfScope ps("layer_rnn_backward_weights", ws);
+      RnnWgradOpts o;
+      o.max_blocks = side_gemm_blocks(); o.in_bound = input_bound_;
+      o.in_cols = packed_input_cols(T, N); o.pre = wgrad_prepack(in_value, out_value);
       int st = rnn_backward_weights(desc_, ws, T, N, in_value.Data(), out_value.Data(), workspace_.p,
-                                    workspace_.bytes, to_update->grad_.f(), reserve_.p, reserve_.bytes,
-                                    side_gemm_blocks(), input_bound_, nullptr, packed_input_cols(T, N), false,
-                                    wgrad_prepack(in_value, out_value));
+                                    workspace_.bytes, to_update->grad_.f(), reserve_.p, reserve_.bytes, o);
       if (st) throw std::runtime_error("rnn_backward_weights failed: " + std::to_string(st));
     }
     return;
@@ -223,14 +225,15 @@ void CuDNNRecurrentComponent::Backprop(const ChunkInfo &, const ChunkInfo &,
     to_update->grad_stream_ = ws;
     KCTC_HIP_CHECK(hipMemsetAsync(to_update->grad_.p, 0, sizeof(float) * NumParameters(), ws));
     ProfScope ps("layer_rnn_backward_weights", ws);
+    RnnWgradOpts o;
+    o.max_blocks = dev.side ? side_gemm_blocks() : 0; o.in_bound = input_bound_;
     // the bottom component (no input derivative): its weight GEMMs are the
     // step's tail, so dW runs beside dR on the (then idle) dx-stream queue
+    o.s2 = (!in_deriv && dev.side) ? dev.stream2 : nullptr;
+    o.in_cols = packed_input_cols(T, N); o.pre = wgrad_prepack(in_value, out_value);
+    o.beside = in_deriv && dev.side;  // the next component's backward runs beside
     int st = rnn_backward_weights(desc_, ws, T, N, in_value.Data(), out_value.Data(), workspace_.p,
-                                  workspace_.bytes, to_update->grad_.f(), reserve_.p, reserve_.bytes,
-                                  dev.side ? side_gemm_blocks() : 0, input_bound_,
-                                  (!in_deriv && dev.side) ? dev.stream2 : nullptr, packed_input_cols(T, N),
-                                  in_deriv && dev.side,  // the next component's backward runs beside
-                                  wgrad_prepack(in_value, out_value));
+                                  workspace_.bytes, to_update->grad_.f(), reserve_.p, reserve_.bytes, o);
     if (st) throw std::runtime_error("rnn_backward_weights failed: " + std::to_string(st));
   }
 }

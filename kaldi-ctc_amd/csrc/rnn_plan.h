@@ -1,7 +1,8 @@
-// rnn_plan.h -- what the RNN host (rnn.hip) decides once per call, private to
-// csrc/: the workspace view (RnnWs) and the recurrence plan (RecPlan) of
-// rnn_plan.hip.  Both are built per host call and never kept across calls:
-// the environment knobs and the CU budget may change in between.
+// rnn_plan.h -- what the RNN host (the units mapped in rnn.hip) decides once
+// per call, private to csrc/: the workspace view (RnnWs) and the recurrence
+// plan (RecPlan) of rnn_plan.hip.  Both are built per host call and never kept
+// across calls: the environment knobs and the CU budget may change in between.
+// (rnn_host.h, beside this header, declares the steps those units share.)
 #pragma once
 #include <algorithm>
 #include <cstdlib>

@@ -301,11 +301,11 @@ int x3p_pick_split(int M, int N, int KB, int batch) {
 
 // kernel parameters of a gemm_x3p call (t256: it runs on 256 x 256 tiles)
 static PParams x3p_params(const X3PArgs &g, bool &t256) {
-  t256 = !g.stream_flags && x3p_use_256(g.M, g.N);  // large shapes on 256 x 256 tiles
+  t256 = !g.producer.lines && x3p_use_256(g.M, g.N);  // large shapes on 256 x 256 tiles
   PParams p = x3p_problem(g.M, g.N, g.KB, t256 ? TB2 : TB, g.A, g.eA, g.B, g.eB, g.C, g.ldc, g.bias, g.bias2, g.sBias,
                           g.tile_counter,
-                          {g.stream_flags, g.stream_nwg, g.stream_T, g.stream_N, g.stream_rg, g.stream_err,
-                           g.stream_xcd_word, g.stream_xcd_count});
+                          {g.producer.lines, g.producer.nwg, g.stream_T, g.stream_N, g.stream_rg, g.stream_err,
+                           g.producer.xcd_word, g.producer.xcd_count});
   p.sA = g.sA; p.sB = g.sB; p.sC = g.sC; p.seA = g.seA; p.seB = g.seB;
   p.alpha = g.alpha; p.beta = g.beta;
   p.batch = g.batch;
@@ -331,14 +331,14 @@ static void x3p_reduce(hipStream_t s, const PParams &p) {
 
 void gemm_x3p(hipStream_t s, const X3PArgs &g) {
   if (g.M <= 0 || g.N <= 0 || g.batch <= 0) return;
-  if (g.stream_flags && !rnn_side_gated(s))
+  if (g.producer.lines && !rnn_side_gated(s))
     throw std::logic_error("gemm_x3p: streaming launch beside a recurrence without its residency gate");
   bool t256 = false;
   PParams p = x3p_params(g, t256);
   const int total = p.tiles * p.batch * p.split;
   int blocks = total;
   if (g.max_blocks > 0 && total > g.max_blocks) blocks = std::max(8, g.max_blocks / 8 * 8);
-  if (g.stream_flags && g.stream_arrive && g.stream_part && g.KB % 2 == 0 && (long)g.M * g.ldc * 4 + (long)(g.batch - 1) * g.sC * 4 < (1L << 31)) {
+  if (g.producer.lines && g.stream_arrive && g.stream_part && g.KB % 2 == 0 && (long)g.M * g.ldc * 4 + (long)(g.batch - 1) * g.sC * 4 < (1L << 31)) {
     p.sdir = 1;
     p.kbchunk = g.KB / 2;  // the producer's two directions
     p.arrive = g.stream_arrive;
@@ -358,8 +358,8 @@ void gemm_x3p(hipStream_t s, const X3PArgs &g) {
         (long)g.stream_T * g.stream_step * 2 >= (1L << 31))
       throw std::invalid_argument("gemm_x3p: bad streaming arguments");
     // persistent blocks, each owning its CU's LDS, so the producer's
-    // workgroups always find free CUs (max_blocks = CUs left to this GEMM)
-    const int sb = std::min(stream_total(p), g.max_blocks > 0 ? g.max_blocks : 176);
+    // workgroups always find free CUs (producer.blocks = CUs left to this GEMM)
+    const int sb = std::min(stream_total(p), g.producer.blocks > 0 ? g.producer.blocks : 176);
     if (g.bf16) {  // A: the producer's bf16 h images (same chunk addressing, 64 k per block)
       if (p.eB) throw std::invalid_argument("gemm_x3p: bf16 operands take no exponents");
       x3p_launch<gemm_x3p_kernel<true, true>>(dim3(sb), NTH, kLdsStream, s, p);
@@ -378,7 +378,7 @@ void gemm_x3p_pair(hipStream_t s, const X3PArgs &g1, const X3PArgs &g2) {
   if (g1.M <= 0 || g1.N <= 0 || g1.batch <= 0) return gemm_x3p(s, g2);
   bool a = false, b = false;
   PParams p = x3p_params(g1, a), q = x3p_params(g2, b);
-  if (!a || !b || !p.counter || g1.bf16 != g2.bf16 || g1.stream_flags || g2.stream_flags)
+  if (!a || !b || !p.counter || g1.bf16 != g2.bf16 || g1.producer.lines || g2.producer.lines)
     throw std::invalid_argument("gemm_x3p_pair: two 256-tile problems with a tile counter");
   if (g1.bf16 && (p.eA || p.eB || q.eA || q.eB)) throw std::invalid_argument("gemm_x3p: bf16 operands take no exponents");
   const int total = p.tiles * p.batch * p.split + q.tiles * q.batch * q.split;

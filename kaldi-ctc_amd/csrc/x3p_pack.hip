@@ -250,12 +250,11 @@ void bf16_pack_rows(hipStream_t s, const float *X, long ldx, int R, int K, __bf1
   if (!ok) throw std::invalid_argument("bf16_pack_rows: K > 4096");
 }
 
-void bf16_pack_cols(hipStream_t s, const float *X, long ldx, int R, int Cn, int shift, __bf16 *out, int batch, long sX,
-                    long sOut) {
-  if (R <= 0 || Cn <= 0 || batch <= 0) return;
+void bf16_pack_cols(hipStream_t s, const float *X, long ldx, int R, int Cn, int shift, __bf16 *out) {
+  if (R <= 0 || Cn <= 0) return;
   const int KB = (R + 63) / 64;
-  hipLaunchKernelGGL(bf16_pack_cols_kernel, dim3(ceil_div(Cn, 64), KB, batch), dim3(256), 0, s, X, ldx, R, Cn, KB,
-                     shift, sX, out, sOut);
+  hipLaunchKernelGGL(bf16_pack_cols_kernel, dim3(ceil_div(Cn, 64), KB, 1), dim3(256), 0, s, X, ldx, R, Cn, KB, shift,
+                     0L, out, 0L);
 }
 
 void x3p_pack_rows(hipStream_t s, const float *X, long ldx, int R, int K, _Float16 *out, int *eout, float bound,
@@ -273,19 +272,19 @@ void x3p_pack_rows(hipStream_t s, const float *X, long ldx, int R, int K, _Float
 }
 
 void x3p_pack_cols(hipStream_t s, const float *X, long ldx, int R, int Cn, int shift, _Float16 *out, int *eout,
-                   const unsigned *cmax, float bound, int batch, long sX, long sOut, long sE, long sCm,
-                   const unsigned *avoid, int nxcd, int *counter) {
-  if (R <= 0 || Cn <= 0 || batch <= 0) return;
+                   const unsigned *cmax, float bound, PackAvoid avoid) {
+  if (R <= 0 || Cn <= 0) return;
   const int KB = (R + 31) / 32;
-  if (avoid) {
-    const long items = (long)ceil_div(Cn, 64) * ceil_div(KB, KPI) * batch;
-    if (!counter || items + 8 >= (1L << 31)) throw std::invalid_argument("x3p_pack_cols: avoid needs a counter");
+  const long z = 0;  // one matrix: no batch strides
+  if (avoid.word) {
+    const long items = (long)ceil_div(Cn, 64) * ceil_div(KB, KPI);
+    if (!avoid.counter || items + 8 >= (1L << 31)) throw std::invalid_argument("x3p_pack_cols: avoid needs a counter");
     hipLaunchKernelGGL(pack_cols_kernel, dim3((int)std::min<long>((items + 7) / 8, 1024)), dim3(256), 0, s, X, ldx, R,
-                       Cn, KB, shift, sX, out, sOut, eout, sE, cmax, sCm, bound, avoid, nxcd, batch, counter);
+                       Cn, KB, shift, z, out, z, eout, z, cmax, z, bound, avoid.word, avoid.nxcd, 1, avoid.counter);
     return;
   }
-  hipLaunchKernelGGL(pack_cols_kernel, dim3(ceil_div(Cn, 64), ceil_div(KB, KPI), batch), dim3(256), 0, s, X, ldx, R,
-                     Cn, KB, shift, sX, out, sOut, eout, sE, cmax, sCm, bound, nullptr, 0, batch, nullptr);
+  hipLaunchKernelGGL(pack_cols_kernel, dim3(ceil_div(Cn, 64), ceil_div(KB, KPI), 1), dim3(256), 0, s, X, ldx, R, Cn, KB,
+                     shift, z, out, z, eout, z, cmax, z, bound, nullptr, 0, 1, nullptr);
 }
 
 }  // namespace kctc

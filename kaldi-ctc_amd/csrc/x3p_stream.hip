@@ -342,7 +342,9 @@ void gemm_x3p_bwd_stream(hipStream_t s, const X3PBwdStream &a) {
   const bool t256 = x3p_bwd_stream_256(a.M, a.N, a.KB, a.bf16);
   if ((a.forward || a.bias) && !t256) throw std::invalid_argument("gemm_x3p_bwd_stream: forward producer needs 256 tiles");
   PParams p = x3p_problem(a.M, a.N, a.KB, t256 ? TB2 : TB, a.Ap, a.eA, a.B, a.eB, a.C, a.ldc, a.bias, a.bias2, a.sbias,
-                          a.cnt, {a.flags, a.nwg, a.T, a.Nf, a.rg, a.err, a.xcd_word, a.xcd_count});
+                          a.cnt,
+                          {a.producer.lines, a.producer.nwg, a.T, a.Nf, a.rg, a.err, a.producer.xcd_word,
+                           a.producer.xcd_count});
   p.sA = (long)a.M * a.KB * 64; p.seA = a.M; p.sB = a.sB; p.seB = a.seB;
   p.alpha = 1.f; p.beta = 0.f;
   p.batch = 2; p.split = 1; p.kbchunk = a.KB;
@@ -361,7 +363,7 @@ void gemm_x3p_bwd_stream(hipStream_t s, const X3PBwdStream &a) {
   }
   // 128 tiles: tailr = 0, every slot has P pack and gx GEMM jobs
   const int total = 2 * (p.nrt - p.tailr) * (p.P + p.gx) + 2 * p.tailr * (p.P + p.gx * p.tails);
-  const dim3 grid(std::min(total, a.blocks > 0 ? a.blocks : 96));
+  const dim3 grid(std::min(total, a.producer.blocks > 0 ? a.producer.blocks : 96));
   x3p_with_kw<4>(K, [&](auto kw) {
     constexpr int KW = decltype(kw)::value;
     if (t256) {
@@ -407,8 +409,8 @@ void x3p_row_stream_selftest(hipStream_t s, int M, int N, int KB, int forward, i
   a.B = B; a.eB = eB; a.sB = (long)N * KB * 64; a.seB = N;
   a.C = C; a.ldc = N;
   a.part = pt; a.part2 = tr > 0 ? pt2 : nullptr; a.tail_rows = tr; a.cnt = cn;
-  a.flags = flags; a.nwg = 1; a.T = T; a.Nf = Nf; a.err = flags + 1000; a.rg = 1;
-  a.blocks = 64;
+  a.producer.lines = flags; a.producer.nwg = 1; a.producer.blocks = 64;
+  a.T = T; a.Nf = Nf; a.err = flags + 1000; a.rg = 1;
   a.forward = forward != 0;
   a.bias = bias; a.bias_cols = N;
   gemm_x3p_bwd_stream(s, a);

@@ -1,5 +1,5 @@
 """bf16 recurrences write their dGates straight into the packed bf16 operands
-of the dx / dW / dR GEMMs (rnn.hip bf16_direct, RecParams::dxr / dxt / et)
+of the dx / dW / dR GEMMs (rnn_plan.h bf16_direct, RecParams::dxr / dxt / et)
 instead of fp32 rows that pack kernels convert afterwards.  The conversion is
 the same round-to-nearest cast of the same fp32 values, so training is bit
 identical to the packing path (KCTC_BF16_DIRECT=0), for GRU (separate DX and E

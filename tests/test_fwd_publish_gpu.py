@@ -1,4 +1,4 @@
-"""The stacked forward recurrence (rnn.hip rnn_fwd_rec6, kPrecX3S) with 8-row
+"""The stacked forward recurrence (rec6_fwd.hip rnn_fwd_rec6, kPrecX3S) with 8-row
 K partials: a wave folds accumulator register i against register i + 2, writes
 8 rows of float4 partials, and only the element threads of rows 0..7 run the
 reduction reads and the cell.

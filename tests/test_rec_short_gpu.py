@@ -1,5 +1,5 @@
-"""Loop edges of the persistent recurrences (rnn.hip rnn_fwd_rec6 /
-rnn_bwd_rec6) that the longer cases of test_rnn_gpu.py (T >= 9) never reach.
+"""Loop edges of the persistent recurrences (rec6_fwd.hip rnn_fwd_rec6 /
+rec6_bwd.hip rnn_bwd_rec6) that the longer cases of test_rnn_gpu.py (T >= 9) never reach.
 
 The step loops rotate the next step's operands (G row, dy / gates / cell
 state) through registers behind the hand-off, and the self-tagged hand-off

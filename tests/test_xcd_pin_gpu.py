@@ -51,7 +51,7 @@ def test_pinned_bit_identical(kctc, gpu, mode, N, T, var):
     feats, nf, fl, ll = kctc.synth_minibatch(7 + N, T, N, D, A, 0.125)
     batch = (feats, nf, fl, ll, T, N)
     # KCTC_XCD6F: the IO-wave forward, whose pinned form feeds a streamed
-    # projection here (KCTC_FWD_STREAM_PINNED, off by default: rnn.hip
+    # projection here (KCTC_FWD_STREAM_PINNED, off by default: rnn_stream.hip
     # chain_ok) as its unpinned form does; KCTC_XCD6F-stk: the default
     # stacked forward of <= 8-row groups, projections after the recurrence
     env = {"KCTC_FWD_STREAM_PINNED": "1"}
@@ -78,7 +78,7 @@ def test_pinned_bit_identical(kctc, gpu, mode, N, T, var):
 
 @pytest.mark.parametrize("mode", [2, 3])
 def test_stacked_hilo_matches_oracle_grade(kctc, gpu, mode):
-    """KCTC_STK=1 (rnn.hip kPrecX3S: hi / lo of a <= 8-row group stacked in one
+    """KCTC_STK=1 (rec_common.h kPrecX3S: hi / lo of a <= 8-row group stacked in one
     MFMA operand, all four split products) against the default 3-MFMA form:
     not bit-identical (different products and order), but the two agree to
     fp32-class accuracy after two training steps."""
