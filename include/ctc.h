@@ -82,19 +82,21 @@ ctcStatus_t mictc_compute_ctc_loss_async(const float *activations, float *gradie
                                          ctcStream_t stream, int blank_label);
 
 /* TEST / TUNING KNOB, not part of the warp-ctc contract: frames per barrier
- * of the alpha/beta recursion (1..8; default 8, or KCTC_CTC_PAIR read once at
- * the first call).  PROCESS-GLOBAL: every later launch from any thread or
+ * of the alpha/beta recursion (1..8, larger values clamped; default 8).
+ * PROCESS-GLOBAL: every later launch from any thread or
  * network reads it, so set it only while no CTC call is in flight (the tests
  * do, one process).  Returns the previous value; m <= 0 only queries.  Same
  * results for every m (tests/test_ctc_gpu.py). */
 int mictc_set_frame_group(int m);
 
 /* TEST KNOB, not part of the warp-ctc contract: 1 (default) runs the
- * alpha/beta recursion on overlapping per-wave state windows (one
- * log-sum-exp per lane and frame, up to 12 waves), 0 on the 512-thread kernel
- * with halo log-sum-exps.  Process-global like mictc_set_frame_group; same
- * results either way (tests/test_ctc_gpu.py).  Returns the previous value;
- * on < 0 only queries. */
+ * alpha/beta recursion on overlapping per-wave state windows wherever their
+ * 12 waves hold the longest label sequence, and on the long-label kernel (512
+ * threads, 3 states per thread, one barrier per frame) beyond that; 0 runs
+ * the long-label kernel for every batch, so that the tests reach it at small
+ * sizes too.  Process-global like mictc_set_frame_group; same results either
+ * way (tests/test_ctc_gpu.py).  Returns the previous value; on < 0 only
+ * queries. */
 int mictc_set_win(int on);
 
 #ifdef __cplusplus

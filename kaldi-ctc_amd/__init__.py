@@ -78,9 +78,8 @@ def lib():
     L.mictc_compute_ctc_loss_async.restype = ctypes.c_int
     L.mictc_set_frame_group.argtypes = [ctypes.c_int]
     L.mictc_set_frame_group.restype = ctypes.c_int
-    if hasattr(L, "mictc_set_win"):  # (absent from pre-round-6 builds run in A/B comparisons)
-        L.mictc_set_win.argtypes = [ctypes.c_int]
-        L.mictc_set_win.restype = ctypes.c_int
+    L.mictc_set_win.argtypes = [ctypes.c_int]
+    L.mictc_set_win.restype = ctypes.c_int
     _bind_optional(L)
     _lib = L
     return L
@@ -133,8 +132,9 @@ def ctc_frame_group(m=0):
 
 
 def ctc_window_kernel(on=-1):
-    """Overlapping-window alpha/beta kernel on (1, default) / off (0)
-    (mictc_set_win); returns the previous value (on < 0: query only)."""
+    """Overlapping-window alpha/beta kernel on (1, default) / off (0: the
+    long-label kernel for every batch) (mictc_set_win); returns the previous
+    value (on < 0: query only)."""
     return lib().mictc_set_win(int(on))
 
 

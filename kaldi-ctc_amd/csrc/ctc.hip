@@ -8,15 +8,19 @@
 //                      4*A B read + 4*A B written per row).
 //   K2 ctc_alpha_beta  one workgroup per (utterance, direction): log-space
 //                      alpha (forward) or beta (backward) recursion, serial
-//                      over T with ONE workgroup barrier per group of 8 frames
-//                      (ctc_alpha_beta_win: overlapping per-wave state windows,
-//                      the default up to 600 extended labels; ab_body: 512
-//                      threads with halo lanes, 1..3 states per thread).  The
-//                      extended (blank-interleaved) label sequence lives in
-//                      registers, the previous frame's column in double-buffered
-//                      LDS, the emission log-probs (normalised by K1) are
-//                      gathered into LDS a chunk of frames ahead by LDS-DMA.  Each frame is renormalised by the max of
-//                      the previous column (wave max via DPP/shfl, then LDS) and
+//                      over T.  Two kernels, chosen by the longest extended
+//                      label sequence of the batch: ctc_alpha_beta_win
+//                      (overlapping per-wave state windows, up to 12 waves: 600
+//                      extended labels at the default 8 frames per workgroup
+//                      barrier) and, for longer label sequences,
+//                      ctc_alpha_beta (512 threads, 3 states per thread, one
+//                      barrier per frame).  The extended (blank-interleaved)
+//                      label sequence lives in registers, the previous frame's
+//                      column in double-buffered LDS, the emission log-probs
+//                      (normalised by K1) are gathered into LDS a chunk of
+//                      frames ahead by LDS-DMA.  Each frame is renormalised by
+//                      the max of the previous column (wave max via DPP, then
+//                      LDS; inside a window group only its first frame) and
 //                      the running offset is kept in fp64, so exp(alpha+beta-logp)
 //                      keeps ~1e-7 relative accuracy at T=2000 (plain fp32 log
 //                      space -- warp-ctc's own arithmetic -- loses ~1e-3).  The
@@ -26,9 +30,8 @@
 //                      grad = softmax - gamma; padding / infeasible rows get 0.
 //                      Deterministic (fixed summation order, no atomics).
 #include <algorithm>
-#include <cstring>
-#include <type_traits>
 #include <atomic>
+#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -53,21 +56,22 @@ struct UttDesc {
 
 struct Layout {
   size_t desc, labels, links, owner, costs, logz, lp, spill, offs, total;
-  int T_max;
-  long long spill_floats, off_doubles;
+  int T_max, L_max;  // longest utterance, longest label sequence
+  long long nlab;    // labels of the whole batch
 };
 
+// Checks the lengths and lays the workspace out; false: invalid lengths.
 static bool make_layout(const int *label_lengths, const int *input_lengths, int A, int N,
-                        Layout *lay, std::vector<UttDesc> *descs, bool *bad) {
-  *bad = false;
-  if (A <= 0 || N <= 0 || !label_lengths || !input_lengths) { *bad = true; return false; }
-  int T_max = 0;
+                        Layout *lay, std::vector<UttDesc> *descs) {
+  if (A <= 0 || N <= 0 || !label_lengths || !input_lengths) return false;
+  int T_max = 0, L_max = 0;
   long long nlab = 0, spill = 0, offs = 0;
   if (descs) descs->resize(N);
   for (int n = 0; n < N; n++) {
     int T = input_lengths[n], L = label_lengths[n];
-    if (T < 0 || L < 0 || L > kMaxLabel) { *bad = true; return false; }
+    if (T < 0 || L < 0 || L > kMaxLabel) return false;
     T_max = T > T_max ? T : T_max;
+    L_max = L > L_max ? L : L_max;
     int S = 2 * L + 1;
     if (descs) {
       UttDesc &d = (*descs)[n];
@@ -91,8 +95,8 @@ static bool make_layout(const int *label_lengths, const int *input_lengths, int 
   l.offs = p;   p = align_up(p + sizeof(double) * (size_t)offs, 256);
   l.total = p;
   l.T_max = T_max;
-  l.spill_floats = spill;
-  l.off_doubles = offs;
+  l.L_max = L_max;
+  l.nlab = nlab;
   return true;
 }
 
@@ -144,15 +148,17 @@ __device__ __forceinline__ float lse3(float a, float b, float c) {
 // gathered into LDS by LDS-DMA (global_load_lds, one 4-byte gather per lane
 // and state block) while the current chunk is processed, so the serial frame
 // loop itself issues no global load: per frame it reads LDS, computes, spills
-// its column and meets ONE raw s_barrier (lgkmcnt only -- a __syncthreads()
-// would drain the in-flight DMA).  The chunk's DMA is waited for once, at the
+// its column and meets ONE raw s_barrier (the window kernel: one per group of
+// frames; lgkmcnt only -- a __syncthreads() would drain the in-flight DMA).
+// The chunk's DMA is waited for once, at the
 // chunk boundary.  All LDS is one dynamic array (a second __shared__ object
 // makes hipcc wait vmcnt(0) before LDS reads while a DMA is in flight):
-//   emit[2][F][SP] | col[2][CP] | wmax[2][8] | feasible flag
+//   emit[2][F][SP] | col[2][CP] | wmax[2][waves] | feasible flag
+// with `waves` the kernel's largest wave count (kWinWaves / kABWaves).
 struct AbLds {
   int F, SP, CP;
-  int pair;  // frames per barrier (SPT == 1, 1..8): mictc_set_frame_group
-  __device__ __host__ size_t floats() const { return 2 * (size_t)F * SP + 2 * (size_t)CP + 2 * kABWaves + 4; }
+  int pair;  // frames per barrier of the window kernel (1..8): mictc_set_frame_group
+  size_t floats(int waves) const { return 2 * (size_t)F * SP + 2 * (size_t)CP + 2 * waves + 4; }
 };
 
 __device__ __forceinline__ void lds_barrier() {
@@ -161,6 +167,12 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// ---------------------------------------------------------------------------
+// K2, long label sequences (launched for more states than the window kernel's
+// 12 waves hold; correct for any S up to 2 * kMaxLabel + 1 = 1279): 512
+// threads, thread `tid` owns the SPT = 3 states tid + 512 i, and every frame
+// goes through LDS and one barrier.
+// ---------------------------------------------------------------------------
 // the direction is a template parameter of the body: one code path per
 // direction, so the scheduler is free to hoist each frame's LDS reads
 template <bool SPILL, int SPT, bool is_beta>
@@ -209,23 +221,6 @@ __device__ __forceinline__ void ab_body(
   // beta: transition s -> s+2 allowed iff l'_{s+2} != blank and != l'_s; for
   // odd s that is lab[(s+1)/2] != lab[(s-1)/2]; for even s, l'_{s+2} is blank.
 
-  // Groups of m frames per barrier (SPT == 1, m = lay.pair in 2..8): lanes
-  // 0 .. 2(m-1)-1 of each wave also carry halo states of the neighbouring
-  // wave -- alpha: 64 w - 2(m-1) .. 64 w - 1; beta: 64 w + 64 .. -- so frames
-  // 2..m of a group need no exchange: their s - 1 / s - 2 (beta: s + 1 /
-  // s + 2) come from the previous frame's values by wave shuffles, the halo
-  // (shrinking by two states a frame) filling the wave edge.
-  const int gm = SPT == 1 ? max(1, min(lay.pair, 8)) : 1;
-  const int nh = 2 * (gm - 1);
-  const int hs = is_beta ? 64 * wid + 64 + lane : 64 * wid - nh + lane;
-  const bool hlive = lane < nh && hs >= 0 && hs < S;
-  bool hskip = false;
-  if (hlive && (hs & 1)) {
-    if (!is_beta) hskip = (hs >= 2) && (lab[(hs - 1) >> 1] != lab[(hs - 3) >> 1]);
-    else hskip = (hs + 2 < S) && (lab[(hs + 1) >> 1] != lab[(hs - 1) >> 1]);
-  }
-  const bool pair_ok = gm > 1;
-
   const long tstride = (long)N * A;
   const float *lrow = lp + (long)n * A;  // + t * N * A
   float *sp = spill + d.ab_off + (is_beta ? (long long)T * S : 0);
@@ -259,97 +254,6 @@ __device__ __forceinline__ void ab_body(
     for (int f = 0; f < fend; f++) {
       const int k = c * F + f;
       const int t = tframe(k);
-      if (pair_ok && k > 0 && f + 1 < fend) {
-        // frames k .. k + g - 1 with one barrier; mu (the max of column k - 1)
-        // renormalises frame k only
-        const int g = min(gm, fend - f);
-        const int sid = min(tid, SP - 1), hid = min(max(hs, 0), SP - 1);
-        const float *wm = wmax + (cur ^ 1) * kABWaves;
-        const float *pv = colb + (cur ^ 1) * CP;
-        const int s0 = tid;
-        float pa, pb, pc, ha, hb, hc;
-        if (!is_beta) {
-          pa = pv[min(s0, CP - 1)];
-          pb = s0 >= 1 ? pv[max(s0 - 1, 0)] : -INFINITY;
-          pc = skip[0] ? pv[max(s0 - 2, 0)] : -INFINITY;
-          ha = pv[min(hid, CP - 1)];
-          hb = hs >= 1 ? pv[min(max(hs - 1, 0), CP - 1)] : -INFINITY;
-          hc = hskip ? pv[min(max(hs - 2, 0), CP - 1)] : -INFINITY;
-        } else {
-          pa = pv[min(s0, CP - 1)];
-          pb = s0 + 1 < S ? pv[min(s0 + 1, CP - 1)] : -INFINITY;
-          pc = skip[0] ? pv[min(s0 + 2, CP - 1)] : -INFINITY;
-          ha = pv[min(hid, CP - 1)];
-          hb = hs + 1 < S ? pv[min(hs + 1, CP - 1)] : -INFINITY;
-          hc = hskip ? pv[min(hs + 2, CP - 1)] : -INFINITY;
-        }
-        float mu = wm[0];
-#pragma unroll
-        for (int w = 1; w < kABWaves; w++) mu = fmaxf(mu, wm[w]);
-        off += (double)mu;
-        float q = 0.f, hq = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          if (j >= g) break;
-          const int tj = tframe(k + j);
-          const float ly = em[(size_t)(f + j) * SP + sid];
-          const float hly = em[(size_t)(f + j) * SP + hid];
-          if (j > 0) {
-            // the previous frame's values of s - 1, s - 2 (beta: s + 1, s + 2)
-            // from the neighbouring lanes, the halo at the wave edge
-            // whole-wave DPP shifts (wave_shr:1 / wave_shl:1); the edge lane
-            // takes `old` -- the halo value broadcast by readlane
-            constexpr int kShr1 = 0x138, kShl1 = 0x130;
-            auto dpp = [](float old, float src, auto ctrl) {
-              return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src),
-                                                                decltype(ctrl)::value, 0xf, 0xf, false));
-            };
-            const int ninf = __float_as_int(-INFINITY);
-            (void)ninf;
-            if (!is_beta) {
-              const float e1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hq), nh - 1));  // 64 w - 1
-              const float e2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hq), nh - 2));  // 64 w - 2
-              using R = std::integral_constant<int, kShr1>;
-              const float b1 = dpp(e1, q, R{});   // lane l: q[l-1]; lane 0: 64 w - 1
-              const float c1 = dpp(e2, b1, R{});  // lane l: q[l-2]; lane 1: 64 w - 1; lane 0: 64 w - 2
-              const float g1 = dpp(-INFINITY, hq, R{}), g2 = dpp(-INFINITY, g1, R{});
-              pa = q;
-              pb = s0 >= 1 ? b1 : -INFINITY;
-              pc = skip[0] ? c1 : -INFINITY;
-              ha = hq;
-              hb = hs >= 1 ? g1 : -INFINITY;
-              hc = hskip ? g2 : -INFINITY;
-            } else {
-              const float e0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hq), 0));  // 64 w + 64
-              const float e1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hq), 1));  // 64 w + 65
-              using L = std::integral_constant<int, kShl1>;
-              const float b1 = dpp(e0, q, L{});   // lane l: q[l+1]; lane 63: 64 w + 64
-              const float c1 = dpp(e1, b1, L{});  // lane l: q[l+2]; lane 62: 64 w + 64; lane 63: 64 w + 65
-              const float g1 = dpp(-INFINITY, hq, L{}), g2 = dpp(-INFINITY, g1, L{});
-              pa = q;
-              pb = s0 + 1 < S ? b1 : -INFINITY;
-              pc = skip[0] ? c1 : -INFINITY;
-              ha = hq;
-              hb = lane + 1 < nh && hs + 1 < S ? g1 : -INFINITY;
-              hc = lane + 2 < nh && hskip ? g2 : -INFINITY;
-            }
-          }
-          const float m = j == 0 ? mu : 0.f;
-          const float v = lse3(pa, pb, pc) - m;
-          q = s0 < S ? v + ly : -INFINITY;
-          hq = hlive ? (lse3(ha, hb, hc) - m) + hly : -INFINITY;
-          if (SPILL && s0 < S) sp[(long)tj * S + s0] = is_beta ? v : q;
-          if (tid == 0 && SPILL) op[tj] = off;
-        }
-        float *cc = colb + cur * CP;
-        cc[s0] = q;
-        float lm = wave_max_l63(q);
-        if (lane == 63) wmax[cur * kABWaves + wid] = lm;
-        lds_barrier();
-        cur ^= 1;
-        f += g - 1;
-        continue;
-      }
       float ly[SPT];
 #pragma unroll
       for (int i = 0; i < SPT; i++) ly[i] = em[(size_t)f * SP + min(tid + i * kABThreads, SP - 1)];
@@ -434,11 +338,11 @@ __device__ __forceinline__ void ab_body(
 }
 
 // ---------------------------------------------------------------------------
-// K2, overlapping windows (S <= kWinWaves x own states; the default path).
-// Frames go in groups of m per barrier as in ab_body, but instead of a second
-// log-sum-exp per lane for the halo, each wave's 64 lanes hold a WINDOW of 64
-// consecutive states: `own` = 64 - 2 (m - 1) of them its own, the other
-// 2 (m - 1) the neighbour's edge (alpha: the states below, beta: above).
+// K2, overlapping windows (S <= kWinWaves x own states).
+// Frames go in groups of m = lay.pair per barrier.  Each wave's 64 lanes hold
+// a WINDOW of 64 consecutive states: `own` = 64 - 2 (m - 1) of them its own,
+// the other 2 (m - 1) the neighbour's edge (alpha: the states below, beta:
+// above).
 // Within a group the previous frame's s - 1 / s - 2 (beta: s + 1 / s + 2) come
 // from the neighbouring lanes by whole-wave DPP shifts; the lanes a shift
 // cannot feed (the window's far edge) go stale by two per frame, which after
@@ -446,7 +350,8 @@ __device__ __forceinline__ void ab_body(
 // every lane computes ONE log-sum-exp per frame.  The group's first frame
 // reads the whole previous column from LDS (own states written by their
 // waves at the group's end) and carries the renormalisation.  Same spill,
-// offsets and costs as ab_body; more waves (ceil(S / own), up to 12 at m = 8).
+// offsets and costs as the long-label kernel writes; ceil(S / own) waves, up to
+// kWinWaves.
 constexpr int kWinWaves = 12;
 template <bool SPILL, bool is_beta>
 __device__ __forceinline__ void win_body(const float *__restrict__ lp, int N, int A, int blank,
@@ -482,7 +387,9 @@ __device__ __forceinline__ void win_body(const float *__restrict__ lp, int N, in
   const int s = is_beta ? own * wid + lane : own * wid - nh + lane;  // this lane's state
   const bool mine = is_beta ? lane < own : lane >= nh;
   const bool live = s >= 0 && s < S;
-  bool skip = false;  // alpha: s - 2 -> s allowed; beta: s + 2 -> s (see ab_body)
+  // alpha: s - 2 -> s allowed iff l'_s != blank and != l'_{s-2}; beta: s -> s + 2
+  // iff l'_{s+2} != blank and != l'_s, for odd s lab[(s+1)/2] != lab[(s-1)/2]
+  bool skip = false;
   if (live && (s & 1)) {
     if (!is_beta) skip = (s >= 2) && (lab[(s - 1) >> 1] != lab[(s - 3) >> 1]);
     else skip = (s + 2 < S) && (lab[(s + 1) >> 1] != lab[(s - 1) >> 1]);
@@ -721,35 +628,44 @@ static void staging_release(hipStream_t stream) {
   if (hipEventRecord(g_stage.ev, stream) == hipSuccess) g_stage.pending = true;
 }
 
-// frames per barrier of ctc_alpha_beta (mictc_set_frame_group)
-static std::atomic<int> g_frame_group{0};
-static int frame_group() {
-  int m = g_frame_group.load(std::memory_order_relaxed);
-  if (m <= 0) {
-    m = 8;
-    int expect = 0;
-    g_frame_group.compare_exchange_strong(expect, m);
-    m = g_frame_group.load(std::memory_order_relaxed);
-  }
-  return m;
+// frames per barrier of ctc_alpha_beta_win, 1..8 (mictc_set_frame_group)
+static std::atomic<int> g_frame_group{8};
+// 0: the long-label kernel for every batch (mictc_set_win, for the tests)
+static std::atomic<int> g_win{1};
+
+// K2.  The window kernel wherever its kWinWaves waves hold the batch's longest
+// extended label sequence (Smax states), else the long-label kernel.
+static ctcStatus_t launch_alpha_beta(int Smax, bool want, const float *lp, int N, int A, int blank,
+                                     UttDesc *descs, const int *labels, float *spill, double *offs,
+                                     double *costs, hipStream_t stream) {
+  AbLds al;
+  al.pair = g_frame_group.load(std::memory_order_relaxed);  // measured: 8 < 6 < 4 < 3 < 1 < 2 (ms)
+  const int own = 64 - 2 * (al.pair - 1);
+  const int nwv = (Smax + own - 1) / own;
+  const bool win = nwv <= kWinWaves && g_win.load(std::memory_order_relaxed) != 0;
+  al.SP = (Smax + 63) / 64 * 64;
+  // the long-label kernel writes all kSPT * kABThreads column entries
+  al.CP = std::max((Smax + 4 + 3) / 4 * 4, win ? own * nwv : kSPT * kABThreads);
+  // chunk depth: as many frames as fit 96 KB of double-buffered emissions (4..32)
+  al.F = (int)std::min<size_t>(32, std::max<size_t>(4, (size_t)96 * 1024 / (2 * sizeof(float) * al.SP)));
+  const size_t shm = sizeof(float) * al.floats(win ? kWinWaves : kABWaves);
+  if (shm > 160 * 1024) return CTC_STATUS_INVALID_VALUE;
+  const auto kern = win ? (want ? ctc_alpha_beta_win<true> : ctc_alpha_beta_win<false>)
+                        : (want ? ctc_alpha_beta<true, kSPT> : ctc_alpha_beta<false, kSPT>);
+  ProfSpan ps(stream, "ctc_alpha_beta");
+  (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)shm);
+  // alpha workgroups, then (for the gradient) beta workgroups
+  hipLaunchKernelGGL(kern, dim3(want ? 2 * N : N), dim3(win ? 64 * nwv : kABThreads), shm, stream, lp, N, A, blank,
+                     descs, labels, spill, offs, costs, al);
+  return CTC_STATUS_SUCCESS;
 }
 
-// the overlapping-window alpha / beta kernel (default; mictc_set_win(0): the
-// 512-thread ab_body kernel with halo log-sum-exps, as before round 6)
-static std::atomic<int> g_win{1};
-static bool win_enabled() { return g_win.load(std::memory_order_relaxed) != 0; }
-
-static ctcStatus_t launch(const float *acts, float *grads, const int *flat_labels,
-                          const int *label_lengths, const int *input_lengths, int A, int N,
+static ctcStatus_t launch(const Layout &lay, const std::vector<UttDesc> &descs, const float *acts, float *grads,
+                          const int *flat_labels, const int *label_lengths, int A, int N,
                           double *costs_dev, void *workspace, hipStream_t stream, int blank) {
-  Layout lay;
-  std::vector<UttDesc> descs;
-  bool bad = false;
-  if (!make_layout(label_lengths, input_lengths, A, N, &lay, &descs, &bad) || bad)
-    return CTC_STATUS_INVALID_VALUE;
   if (blank < 0 || blank >= A || !acts || !workspace) return CTC_STATUS_INVALID_VALUE;
-  long long nlab = 0;
-  for (int n = 0; n < N; n++) nlab += label_lengths[n];
+  const long long nlab = lay.nlab;
   for (long long i = 0; i < nlab; i++)
     if (flat_labels[i] < 0 || flat_labels[i] >= A || flat_labels[i] == blank)
       return CTC_STATUS_INVALID_VALUE;
@@ -792,54 +708,12 @@ static ctcStatus_t launch(const float *acts, float *grads, const int *flat_label
     hipLaunchKernelGGL(ctc_logz, dim3(ceil_div(rows, 4)), dim3(256), 0, stream, acts, A, rows,
                        d_logz, d_lp);
   }
-  const int want = grads != nullptr;
-  {
-    int Smax = 1;
-    for (int n = 0; n < N; n++) Smax = 2 * label_lengths[n] + 1 > Smax ? 2 * label_lengths[n] + 1 : Smax;
-    AbLds al;
-    al.pair = frame_group();  // measured: 8 < 6 < 4 < 3 < 1 < 2 (ms)
-    al.SP = (Smax + 63) / 64 * 64;
-    // overlapping windows (ctc_alpha_beta_win) up to kWinWaves waves
-    const int own = 64 - 2 * (std::max(1, std::min(al.pair, 8)) - 1);
-    const int nwv = std::max(1, (Smax + own - 1) / own);
-    if (nwv <= kWinWaves && win_enabled()) {
-      al.CP = std::max((Smax + 4 + 3) / 4 * 4, own * nwv);
-      al.F = (int)std::min<size_t>(32, std::max<size_t>(4, (size_t)96 * 1024 / (2 * sizeof(float) * al.SP)));
-      const size_t shm = sizeof(float) * (2 * (size_t)al.F * al.SP + 2 * (size_t)al.CP + 2 * kWinWaves + 4);
-      if (shm > 160 * 1024) return CTC_STATUS_INVALID_VALUE;
-      ProfSpan ps(stream, "ctc_alpha_beta");
-      auto kern = want ? ctc_alpha_beta_win<true> : ctc_alpha_beta_win<false>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)shm);
-      hipLaunchKernelGGL(kern, dim3(want ? 2 * N : N), dim3(64 * nwv), shm, stream, d_lp, N, A, blank, d_desc, d_lab,
-                         d_spill, d_offs, costs_dev, al);
-    } else {
-      al.CP = std::max((Smax + 4 + 3) / 4 * 4, (Smax <= kABThreads ? 1 : kSPT) * kABThreads);
-      // chunk depth: as many frames as fit 96 KB of double-buffered emissions (4..32)
-      al.F = (int)std::min<size_t>(32, std::max<size_t>(4, (size_t)96 * 1024 / (2 * sizeof(float) * al.SP)));
-      const size_t shm = sizeof(float) * al.floats();
-      if (shm > 160 * 1024) return CTC_STATUS_INVALID_VALUE;
-      ProfSpan ps(stream, "ctc_alpha_beta");
-      auto go = [&](auto kern, int grid) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)shm);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kABThreads), shm, stream, d_lp, N, A, blank, d_desc, d_lab,
-                           d_spill, d_offs, costs_dev, al);
-      };
-      // one state per thread up to 512 extended labels (L <= 255), else three
-      if (Smax <= kABThreads) {
-        if (want) go(ctc_alpha_beta<true, 1>, 2 * N);
-        else go(ctc_alpha_beta<false, 1>, N);
-      } else {
-        if (want) go(ctc_alpha_beta<true, kSPT>, 2 * N);
-        else go(ctc_alpha_beta<false, kSPT>, N);
-      }
-    }
-  }
+  const bool want = grads != nullptr;
+  const int Lmax = lay.L_max, Smax = 2 * Lmax + 1;
+  const ctcStatus_t st = launch_alpha_beta(Smax, want, d_lp, N, A, blank, d_desc, d_lab, d_spill, d_offs,
+                                           costs_dev, stream);
+  if (st != CTC_STATUS_SUCCESS) return st;
   if (want && lay.T_max > 0) {
-    int Lmax = 0;
-    for (int n = 0; n < N; n++) Lmax = label_lengths[n] > Lmax ? label_lengths[n] : Lmax;
-    const int Smax = 2 * Lmax + 1;
     size_t shm = sizeof(float) * kFR * Smax + sizeof(int) * (Lmax > 0 ? Lmax : 1) +
                  sizeof(int) * A + 2 * sizeof(float) * kFR;
     if (shm > 160 * 1024) return CTC_STATUS_INVALID_VALUE;
@@ -863,7 +737,7 @@ extern "C" {
 int get_warpctc_version(void) { return 2; }
 
 int mictc_set_frame_group(int m) {
-  const int prev = frame_group();
+  const int prev = g_frame_group.load();
   if (m > 0) g_frame_group.store(std::max(1, std::min(m, 8)));
   return prev;
 }
@@ -890,9 +764,7 @@ ctcStatus_t get_workspace_size(const int *const label_lengths, const int *const 
                                size_t *size_bytes) {
   if (!size_bytes || info.loc != CTC_GPU) return CTC_STATUS_INVALID_VALUE;
   Layout lay;
-  bool bad = false;
-  if (!make_layout(label_lengths, input_lengths, alphabet_size, minibatch, &lay, nullptr, &bad) ||
-      bad)
+  if (!make_layout(label_lengths, input_lengths, alphabet_size, minibatch, &lay, nullptr))
     return CTC_STATUS_INVALID_VALUE;
   *size_bytes = lay.total;
   return CTC_STATUS_SUCCESS;
@@ -905,9 +777,12 @@ ctcStatus_t mictc_compute_ctc_loss_async(const float *activations, float *gradie
                                          ctcStream_t stream, int blank_label) {
   if (!costs_dev) return CTC_STATUS_INVALID_VALUE;
   try {
-    return launch(activations, gradients, flat_labels, label_lengths, input_lengths,
-                  alphabet_size, minibatch, costs_dev, workspace,
-                  reinterpret_cast<hipStream_t>(stream), blank_label);
+    Layout lay;
+    std::vector<UttDesc> descs;
+    if (!make_layout(label_lengths, input_lengths, alphabet_size, minibatch, &lay, &descs))
+      return CTC_STATUS_INVALID_VALUE;
+    return launch(lay, descs, activations, gradients, flat_labels, label_lengths, alphabet_size, minibatch,
+                  costs_dev, workspace, reinterpret_cast<hipStream_t>(stream), blank_label);
   } catch (...) {
     return CTC_STATUS_UNKNOWN_ERROR;
   }
@@ -918,25 +793,27 @@ ctcStatus_t compute_ctc_loss(const float *const activations, float *gradients,
                              const int *const input_lengths, int alphabet_size, int minibatch,
                              float *costs, void *workspace, struct ctcOptions options) {
   if (options.loc != CTC_GPU || !costs) return CTC_STATUS_INVALID_VALUE;
-  Layout lay;
-  bool bad = false;
-  if (!make_layout(label_lengths, input_lengths, alphabet_size, minibatch, &lay, nullptr, &bad) ||
-      bad)
-    return CTC_STATUS_INVALID_VALUE;
   hipStream_t stream = reinterpret_cast<hipStream_t>(options.stream);
-  double *d_costs = reinterpret_cast<double *>(static_cast<char *>(workspace) + lay.costs);
-  ctcStatus_t st = mictc_compute_ctc_loss_async(activations, gradients, flat_labels,
-                                                label_lengths, input_lengths, alphabet_size,
-                                                minibatch, d_costs, workspace, options.stream,
-                                                options.blank_label);
-  if (st != CTC_STATUS_SUCCESS) return st;
-  std::vector<double> hc(minibatch);
-  if (hipMemcpyAsync(hc.data(), d_costs, sizeof(double) * minibatch, hipMemcpyDeviceToHost,
-                     stream) != hipSuccess)
-    return CTC_STATUS_MEMOPS_FAILED;
-  if (hipStreamSynchronize(stream) != hipSuccess) return CTC_STATUS_EXECUTION_FAILED;
-  for (int n = 0; n < minibatch; n++) costs[n] = (float)hc[n];
-  return CTC_STATUS_SUCCESS;
+  try {
+    Layout lay;
+    std::vector<UttDesc> descs;
+    if (!make_layout(label_lengths, input_lengths, alphabet_size, minibatch, &lay, &descs))
+      return CTC_STATUS_INVALID_VALUE;
+    // the costs go through the workspace's own slot
+    double *d_costs = reinterpret_cast<double *>(static_cast<char *>(workspace) + lay.costs);
+    ctcStatus_t st = launch(lay, descs, activations, gradients, flat_labels, label_lengths, alphabet_size,
+                            minibatch, d_costs, workspace, stream, options.blank_label);
+    if (st != CTC_STATUS_SUCCESS) return st;
+    std::vector<double> hc(minibatch);
+    if (hipMemcpyAsync(hc.data(), d_costs, sizeof(double) * minibatch, hipMemcpyDeviceToHost,
+                       stream) != hipSuccess)
+      return CTC_STATUS_MEMOPS_FAILED;
+    if (hipStreamSynchronize(stream) != hipSuccess) return CTC_STATUS_EXECUTION_FAILED;
+    for (int n = 0; n < minibatch; n++) costs[n] = (float)hc[n];
+    return CTC_STATUS_SUCCESS;
+  } catch (...) {
+    return CTC_STATUS_UNKNOWN_ERROR;
+  }
 }
 
 }  // extern "C"

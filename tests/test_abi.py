@@ -28,6 +28,15 @@ def test_warpctc_status_strings(kctc):
     assert L.get_warpctc_version() >= 1
 
 
+def test_ctc_frame_group_default_query_and_clamp(kctc):
+    assert kctc.ctc_frame_group(0) == 8           # the default; m <= 0 only queries
+    try:
+        assert kctc.ctc_frame_group(3) == 8 and kctc.ctc_frame_group() == 3
+        assert kctc.ctc_frame_group(20) == 3 and kctc.ctc_frame_group(-1) == 8  # clamped to 1..8
+    finally:
+        kctc.ctc_frame_group(8)
+
+
 def test_workspace_size_and_invalid_values(kctc):
     L = kctc.lib()
     ll = np.array([3, 0], np.int32)

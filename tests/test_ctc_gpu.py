@@ -1,6 +1,8 @@
 """CTC HIP kernel parity (warp-ctc ABI, include/ctc.h) vs the fp64 oracle and
 the golden fixtures.  Tolerance (BASELINE north_star): costs and gradients
 within 1e-4 relative; we hold the kernel to 2e-5 (norm-wise on gradients)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -42,8 +44,11 @@ def test_ctc_matches_golden(kctc, gpu, name):
 
 @pytest.fixture(params=[8, 1, 2, 5], ids=lambda m: f"group{m}")
 def frame_group(kctc, request):
-    """Frames per barrier of the alpha/beta kernel (default 8): the halo
-    lanes and DPP shifts of every group depth give the same results."""
+    """Frames per barrier of the alpha/beta recursion (default 8).  The window
+    kernel gives each wave 64 - 2 (m - 1) own states and takes up to 12 waves
+    (S <= 600, 768, 744, 672 at m = 8, 1, 2, 5); longer label sequences run
+    the long-label kernel, which has one barrier per frame at every m.  Every
+    depth gives the same results."""
     prev = kctc.ctc_frame_group(request.param)
     yield request.param
     kctc.ctc_frame_group(prev)
@@ -51,24 +56,20 @@ def frame_group(kctc, request):
 
 @pytest.fixture(params=[1, 0], ids=lambda w: "win" if w else "halo")
 def window(kctc, request):
-    """alpha/beta on overlapping per-wave state windows (default, S <= 600 at
-    8 frames per barrier) or on the 512-thread kernel with halo lanes."""
+    """1 (default): the library picks the alpha/beta kernel, the window kernel
+    up to 12 waves of states and the long-label kernel beyond.  0: the
+    long-label kernel for every batch, so that it runs at every size below its
+    threshold as well.  (The id "halo" dates from the kernel that setting used
+    to select up to S = 512; it stays so that the cases keep their ids.)"""
     prev = kctc.ctc_window_kernel(request.param)
     yield request.param
     kctc.ctc_window_kernel(prev)
 
 
-@pytest.mark.parametrize("seed,T,N,L,A,rep", [
-    (1, 2000, 16, 237, 41, False),     # configs[1] shape: T_max=2000, N=16, L=T/8
-    (2, 667, 8, 250, 41, False),       # configs[2] (fs=3): L = 3T/8
-    (3, 300, 4, 60, 41, True),         # repeats in labels
-    (4, 1300, 2, 639, 41, False),      # maximum label length (MAX_WARPCTC_LABEL_LENGTH)
-    (5, 50, 3, 5, 300, False),         # large alphabet
-    (6, 37, 5, 9, 41, True),           # T not a multiple of any group depth, short utterances
-    (7, 900, 3, 290, 41, True),        # 512 < S <= 600: the window kernel's 12 waves (halo: 3 states per thread)
-])
-def test_ctc_matches_oracle(kctc, gpu, oracle, window, frame_group, seed, T, N, L, A, rep):
-    assert kctc.ctc_frame_group() == frame_group and kctc.ctc_window_kernel() == window
+@functools.lru_cache(maxsize=None)
+def _case(oracle, seed, T, N, L, A, rep):
+    """A seeded batch and its fp64 oracle results, computed once per shape and
+    shared (read-only) by every test, kernel and frame group that uses it."""
     rng = np.random.default_rng(seed)
     acts = (rng.standard_normal((T, N, A)) * 3).astype(np.float32)
     lens = [T - int(rng.integers(0, T // 10 + 1)) if n else T for n in range(N)]
@@ -78,14 +79,73 @@ def test_ctc_matches_oracle(kctc, gpu, oracle, window, frame_group, seed, T, N, 
     il = np.array(lens, np.int32)
     for n, t in enumerate(lens):
         acts[t:, n, :] = 0
+    case = (acts, flat, ll, il) + tuple(oracle.ctc(acts.astype(np.float64), flat, ll, il))
+    for x in case:
+        x.setflags(write=False)
+    return case
+
+
+ROW8 = (8, 700, 2, 301, 41, True)
+
+
+@pytest.mark.parametrize("seed,T,N,L,A,rep", [
+    (1, 2000, 16, 237, 41, False),     # configs[1] shape: T_max=2000, N=16, L=T/8
+    (2, 667, 8, 250, 41, False),       # configs[2] (fs=3): L = 3T/8
+    (3, 300, 4, 60, 41, True),         # repeats in labels
+    (4, 1300, 2, 639, 41, False),      # maximum label length (MAX_WARPCTC_LABEL_LENGTH): long-label kernel, S = 1279
+    (5, 50, 3, 5, 300, False),         # large alphabet
+    (6, 37, 5, 9, 41, True),           # T not a multiple of any group depth, short utterances
+    (7, 900, 3, 290, 41, True),        # S = 581: the window kernel's 12 waves at 8 frames per barrier; halo: the
+                                       # long-label kernel with a nearly empty second state block
+    ROW8,                              # S = 603: first size past the window kernel at group 8 (long-label kernel,
+                                       # second state block almost empty); groups 1, 2, 5: 10, 10, 11 window waves
+    (9, 800, 2, 383, 41, False),       # S = 767: the window kernel's largest extent (12 waves x 64 own states) at
+                                       # group 1, the long-label kernel at every other depth
+])
+def test_ctc_matches_oracle(kctc, gpu, oracle, window, frame_group, seed, T, N, L, A, rep):
+    assert kctc.ctc_frame_group() == frame_group and kctc.ctc_window_kernel() == window
+    acts, flat, ll, il, rc, rg = _case(oracle, seed, T, N, L, A, rep)
     costs, grads = _run(kctc, gpu, acts, flat, ll, il)
-    rc, rg = oracle.ctc(acts.astype(np.float64), flat, ll, il)
     np.testing.assert_allclose(costs, rc, rtol=1e-5)
     # fp32 alpha/beta over T=2000 frames: the within-frame relative error of
     # gamma grows like sqrt(T) * ulp; measured ~2.6e-5 (north_star bar: 1e-4)
     assert rel_err(grads, rg) < 5e-5
     # size-independent property: each real frame's gradient sums to 0
     np.testing.assert_allclose(grads.sum(-1), 0, atol=1e-4)
+
+
+@pytest.mark.parametrize("seed,T,N,L,A,rep", [
+    (10, 120, 3, 50, 41, True),        # window kernel at every depth
+    ROW8,                              # long-label kernel at group 8, window kernel below
+])
+def test_ctc_costs_only_matches_oracle(kctc, gpu, oracle, window, frame_group, seed, T, N, L, A, rep):
+    """want_grad=False launches the alpha half alone, without the column spill
+    (the SPILL = false instantiation of either kernel)."""
+    assert kctc.ctc_frame_group() == frame_group and kctc.ctc_window_kernel() == window
+    acts, flat, ll, il, rc, _ = _case(oracle, seed, T, N, L, A, rep)
+    costs, grads = _run(kctc, gpu, acts, flat, ll, il, want_grad=False)
+    assert grads is None
+    np.testing.assert_allclose(costs, rc, rtol=1e-5)
+
+
+def test_ctc_edge_shapes(kctc, gpu, oracle, window, frame_group):
+    """One batch with a one-frame utterance, an empty label sequence, a repeat,
+    and utterances shorter than one chunk of frames beside one of S = 33."""
+    assert kctc.ctc_frame_group() == frame_group and kctc.ctc_window_kernel() == window
+    labels = [[3], [], [2, 2, 5, 1], [4], [1, 2] * 8]
+    il = np.array([1, 5, 9, 2, 33], np.int32)
+    ll = np.array([len(l) for l in labels], np.int32)
+    flat = np.array([x for l in labels for x in l], np.int32)
+    acts = (np.random.default_rng(11).standard_normal((33, 5, 7)) * 3).astype(np.float32)
+    for n, t in enumerate(il):
+        acts[t:, n, :] = 0
+    rc, rg = oracle.ctc(acts.astype(np.float64), flat, ll, il)
+    assert np.all(np.isfinite(rc)) and np.all(rc > 0)
+    costs, grads = _run(kctc, gpu, acts, flat, ll, il)
+    np.testing.assert_allclose(costs, rc, rtol=1e-5)
+    assert rel_err(grads, rg) < 5e-5
+    for n, t in enumerate(il):
+        assert np.all(grads[t:, n, :] == 0)
 
 
 def test_ctc_costs_only(kctc, gpu, oracle):
