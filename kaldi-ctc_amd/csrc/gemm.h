@@ -1,8 +1,8 @@
 // gemm.h -- fp32 MFMA GEMM for gfx950 (v_mfma_f32_16x16x4_f32, exact fp32).
 // Replaces the cublasSgemm calls of the reference's CuMatrix::AddMatMat
 // (src/cudamatrix/cu-matrix.cc:1077-1110) and cuDNN's internal gate GEMMs.
-// Also gemm.hip's reductions: absmax_f32 and colsum_f32.  The split-fp16 /
-// bf16 GEMM on packed operands has its own header, gemm_x3p.h.
+// Also gemm.hip's reduction absmax_f32.  The split-fp16 / bf16 GEMM on packed
+// operands has its own header, gemm_x3p.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,13 +37,12 @@ struct GemmArgs {
 void gemm_f32(hipStream_t stream, const GemmArgs &g);
 // Heuristic split-K so that tiles * split fill the chip; returns 1 if not needed.
 int gemm_pick_split(int M, int N, int K, int batch);
+// Slabs gemm_f32 runs for a split_k request: chunks of ceil(K / split_k)
+// rounded up to the k tile, so it can be fewer than asked (1: no split)
+int gemm_split_used(int K, int split_k);
 
 // max |X| per row (rmax[b][r]) and per column (cmax[b][c]) as float bits; either may be null
 void absmax_f32(hipStream_t stream, const float *X, long ldx, int rows, int cols, unsigned *rmax, unsigned *cmax,
                 int batch = 1, long strideX = 0, long strideR = 0, long strideC = 0);
-
-// column sums: out[b][j] (+)= alpha * sum_i X[b][i*ldx + j], i < rows  (accumulate if beta=1)
-void colsum_f32(hipStream_t stream, const float *X, long ldx, int rows, int cols, float alpha,
-                float beta, float *out, int batch = 1, long strideX = 0, long strideOut = 0);
 
 }  // namespace kctc

@@ -303,25 +303,6 @@ __global__ __launch_bounds__(256) void splitk_reduce(KParams p) {
   }
 }
 
-__global__ __launch_bounds__(256) void colsum_kernel(const float *__restrict__ X, long ldx, int rows,
-                                                     int cols, float alpha, float beta,
-                                                     float *__restrict__ out, long strideX,
-                                                     long strideOut) {
-  __shared__ float part[4][64];
-  const int b = blockIdx.y, c = blockIdx.x * 64 + (threadIdx.x & 63), g = threadIdx.x >> 6;
-  const float *x = X + (long)b * strideX;
-  float s = 0.f;
-  if (c < cols)
-    for (int r = g; r < rows; r += 4) s += x[(long)r * ldx + c];
-  part[g][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (g == 0 && c < cols) {
-    float v = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
-    float *o = out + (long)b * strideOut + c;
-    *o = alpha * v + (beta != 0.f ? beta * *o : 0.f);
-  }
-}
-
 }  // namespace
 
 int gemm_pick_split(int M, int N, int K, int batch) {
@@ -334,6 +315,11 @@ int gemm_pick_split(int M, int N, int K, int batch) {
   return want < 1 ? 1 : (int)want;
 }
 
+int gemm_split_used(int K, int split_k) {
+  if (split_k <= 1 || K <= 0) return 1;  // K = 0: no chunk to size, the epilogue alone
+  return ceil_div(K, (long)align_up((size_t)ceil_div(K, split_k), BK));
+}
+
 void gemm_f32(hipStream_t stream, const GemmArgs &g) {
   if (g.M <= 0 || g.N <= 0 || g.batch <= 0) return;
   KParams p;
@@ -344,9 +330,8 @@ void gemm_f32(hipStream_t stream, const GemmArgs &g) {
   p.gx = ceil_div(g.N, BN);
   p.tiles = p.gx * ceil_div(g.M, BM);
   p.batch = g.batch;
-  p.split = (g.split_k > 1 && g.ws) ? g.split_k : 1;
-  p.kchunk = p.split > 1 ? (int)align_up((size_t)ceil_div(g.K, p.split), BK) : (g.K > 0 ? g.K : 1);
-  if (p.split > 1) p.split = ceil_div(g.K, p.kchunk);
+  p.split = g.ws ? gemm_split_used(g.K, g.split_k) : 1;
+  p.kchunk = p.split > 1 ? (int)align_up((size_t)ceil_div(g.K, g.split_k), BK) : (g.K > 0 ? g.K : 1);
   p.ws = g.ws;
   auto aligned = [](const void *ptr, long ld, long stride) {
     return ((uintptr_t)ptr % 16 == 0) && (ld % 4 == 0) && (stride % 4 == 0);
@@ -377,13 +362,6 @@ void absmax_f32(hipStream_t stream, const float *X, long ldx, int rows, int cols
   const int rpb = 64;
   hipLaunchKernelGGL(absmax_kernel, dim3(ceil_div(rows, rpb), batch), dim3(256), 0, stream, X, ldx, rows, cols,
                      strideX, rmax, cmax, strideR, strideC, rpb);
-}
-
-void colsum_f32(hipStream_t stream, const float *X, long ldx, int rows, int cols, float alpha,
-                float beta, float *out, int batch, long strideX, long strideOut) {
-  if (cols <= 0 || batch <= 0) return;
-  hipLaunchKernelGGL(colsum_kernel, dim3(ceil_div(cols, 64), batch), dim3(256), 0, stream, X, ldx,
-                     rows, cols, alpha, beta, out, strideX, strideOut);
 }
 
 }  // namespace kctc

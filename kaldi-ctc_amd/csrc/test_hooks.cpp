@@ -5,8 +5,23 @@
 #include <stdexcept>
 
 #include "common.h"
+#include "gemm.h"
 #include "gemm_x3p.h"
 #include "rnn.h"
+
+// runs f, waits for the stream and maps what happened to the hooks' status
+template <typename F>
+static int run_synced(struct ihipStream_t *stream, F &&f) {
+  try {
+    f();
+    KCTC_HIP_CHECK(hipStreamSynchronize(stream));
+    return hipGetLastError() == hipSuccess ? 0 : 3;
+  } catch (const std::invalid_argument &) {
+    return 1;
+  } catch (...) {
+    return 3;
+  }
+}
 
 extern "C" {
 
@@ -65,6 +80,63 @@ int kcm_test_gemm_packed(struct ihipStream_t *stream, int M, int N, int K, int b
   }
   if (buf) (void)hipFree(buf);
   return rc;
+}
+
+int kcm_test_gemm_f32(struct ihipStream_t *stream, int transA, int transB, int M, int N, int K, float alpha,
+                      float beta, const float *A, long lda, const float *B, long ldb, float *C, long ldc,
+                      const float *bias, const float *bias2, int batch, long strideA, long strideB, long strideC,
+                      long strideBias, int split_k, float *ws, int max_blocks, int *tile_counter, int *split_used) {
+  if (!C || M <= 0 || N <= 0 || K < 0 || batch < 1 || (K > 0 && (!A || !B)) || split_k < -1 || split_k == 0 ||
+      max_blocks < 0)
+    return 1;
+  if (split_k < 0) split_k = kctc::gemm_pick_split(M, N, K, batch);
+  if (split_k > 1 && !ws) return 1;
+  kctc::GemmArgs g;
+  g.transA = transA != 0; g.transB = transB != 0;
+  g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta;
+  g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
+  g.bias = bias; g.bias2 = bias2;
+  g.batch = batch; g.strideA = strideA; g.strideB = strideB; g.strideC = strideC; g.strideBias = strideBias;
+  g.split_k = split_k; g.ws = ws; g.max_blocks = max_blocks; g.tile_counter = tile_counter;
+  if (split_used) *split_used = ws ? kctc::gemm_split_used(K, split_k) : 1;
+  return run_synced(stream, [&] { kctc::gemm_f32(stream, g); });
+}
+
+int kcm_test_gemm_pick_split(int M, int N, int K, int batch) { return kctc::gemm_pick_split(M, N, K, batch); }
+int kcm_test_gemm_split_used(int K, int split_k) { return kctc::gemm_split_used(K, split_k); }
+
+int kcm_test_absmax(struct ihipStream_t *stream, const float *X, long ldx, int rows, int cols, unsigned *rmax,
+                    unsigned *cmax, int batch, long strideX, long strideR, long strideC) {
+  if (!X || rows <= 0 || cols <= 0 || batch < 1 || ldx < cols || (!rmax && !cmax)) return 1;
+  return run_synced(stream, [&] {
+    kctc::absmax_f32(stream, X, ldx, rows, cols, rmax, cmax, batch, strideX, strideR, strideC);
+  });
+}
+
+int kcm_test_pack(struct ihipStream_t *stream, int kind, const float *X, long ldx, int R, int KC, int shift,
+                  float bound, int batch, long sX, long sOut, long sE, void *out, int *eout, const unsigned *cmax,
+                  const unsigned *avoid_word, int *counter) {
+  if (kind < 0 || kind > 3 || !X || !out || R <= 0 || KC <= 0 || ldx < KC || batch < 1) return 1;
+  const bool cols = kind == 1 || kind == 3, bf16 = kind >= 2;
+  if (cols ? (batch != 1 || sX || sOut || sE) : shift != 0) return 1;
+  if (bf16 && (bound != 0.f || eout || cmax)) return 1;
+  if (kind == 1 ? (!(bound > 0.f) && !cmax) : cmax != nullptr) return 1;
+  if ((avoid_word || counter) && (kind != 1 || !avoid_word || !counter)) return 1;
+  return run_synced(stream, [&] {
+    _Float16 *oh = static_cast<_Float16 *>(out);
+    __bf16 *ob = static_cast<__bf16 *>(out);
+    switch (kind) {
+      case 0: kctc::x3p_pack_rows(stream, X, ldx, R, KC, oh, eout, bound, batch, sX, sOut, sE); break;
+      case 1: {
+        kctc::PackAvoid avoid;
+        avoid.word = avoid_word; avoid.counter = counter;
+        kctc::x3p_pack_cols(stream, X, ldx, R, KC, shift, oh, eout, cmax, bound, avoid);
+        break;
+      }
+      case 2: kctc::bf16_pack_rows(stream, X, ldx, R, KC, ob, batch, sX, sOut); break;
+      default: kctc::bf16_pack_cols(stream, X, ldx, R, KC, shift, ob); break;
+    }
+  });
 }
 
 int kcm_test_row_stream(struct ihipStream_t *stream, int M, int N, int K, int forward, int tail_rows,

@@ -24,6 +24,38 @@ float kcm_bench_gemm_packed(struct ihipStream_t *stream, int M, int N, int K, in
  * arguments the GEMM refuses, 3 on any other failure. */
 int kcm_test_gemm_packed(struct ihipStream_t *stream, int M, int N, int K, int bf16, int split, int dynamic,
                          int max_blocks, int M2, const float *A, const float *B, float *C, float *C2);
+/* The three hooks below run one library call on device memory that the caller
+ * owns entirely (workspace and counters included, so that it can check guard
+ * regions) and synchronise the stream.  0; 1 on arguments the hook or the
+ * library (std::invalid_argument) refuses; 3 on any other failure.
+ *
+ * gemm_f32 with every field of GemmArgs (gemm.h).  split_k = -1: the split of
+ * gemm_pick_split(M, N, K, batch); ws then needs that many slabs of
+ * batch * M * N floats.  *split_used (may be null): the slabs the launch
+ * runs, 1 without a split. */
+int kcm_test_gemm_f32(struct ihipStream_t *stream, int transA, int transB, int M, int N, int K, float alpha,
+                      float beta, const float *A, long lda, const float *B, long ldb, float *C, long ldc,
+                      const float *bias, const float *bias2, int batch, long strideA, long strideB, long strideC,
+                      long strideBias, int split_k, float *ws, int max_blocks, int *tile_counter, int *split_used);
+/* gemm_pick_split(M, N, K, batch) and gemm_split_used(K, split_k); host code only. */
+int kcm_test_gemm_pick_split(int M, int N, int K, int batch);
+int kcm_test_gemm_split_used(int K, int split_k);
+/* absmax_f32 (gemm.h): float bits of max |X| per row into rmax[b * strideR + r]
+ * and per column into cmax[b * strideC + c]; either may be null. */
+int kcm_test_absmax(struct ihipStream_t *stream, const float *X, long ldx, int rows, int cols, unsigned *rmax,
+                    unsigned *cmax, int batch, long strideX, long strideR, long strideC);
+/* One pack pass of gemm_x3p.h.  kind: 0 x3p_pack_rows, 1 x3p_pack_cols, 2
+ * bf16_pack_rows, 3 bf16_pack_cols.  Rows: R rows of KC values (shift = 0),
+ * batch matrices sX floats, sOut halves and sE ints apart.  Columns: the
+ * transpose of X [R][KC], source row k - shift at k; one matrix (batch = 1,
+ * strides 0).  Split-fp16 kinds: exponents into eout (may be null) from the
+ * data (columns: cmax, float bits of each column's max |x|) or from bound
+ * > 0; the bf16 kinds take neither (bound = 0, eout = cmax = null).
+ * avoid_word / counter (x3p_pack_cols, both or neither): the PackAvoid launch
+ * of 8 XCDs, a zeroed word and a zeroed int. */
+int kcm_test_pack(struct ihipStream_t *stream, int kind, const float *X, long ldx, int R, int KC, int shift,
+                  float bound, int batch, long sX, long sOut, long sE, void *out, int *eout, const unsigned *cmax,
+                  const unsigned *avoid_word, int *counter);
 /* The streamed direction-split GEMM of the RNN backward (dx) and chained forward (next projection) against a
  * producer that has already finished: C[M][N] = E[:, 0:K] Wt[0]^T +
  * E[:, K:2K] Wt[1]^T (+ bias[c]), E [M][2K], Wt [2][N][K], device pointers;
