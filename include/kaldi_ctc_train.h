@@ -192,6 +192,31 @@ int kctc_cu_partition_probe(int part, int nparts, unsigned *ids, int max_ids, in
  * fp32; model files are unaffected. */
 int kctc_nnet_set_precision(kctcNnet_t nnet, int precision);
 
+/* Length-aware training (an extension; off by default, and then nothing
+ * changes).  The reference pads a minibatch to its longest utterance and
+ * cuDNN 5.1 knows no lengths: the reverse direction of every bidirectional
+ * component runs over a shorter utterance's padding before it reaches its
+ * last frame, and the gradient flows back through those steps.  With on = 1
+ * a minibatch of N <= 64 utterances of num_frames[n] in [1, T_max] gives
+ *   - per-utterance costs and best-path ids (real rows) as if each utterance
+ *     were a minibatch of its own (N = 1, T_max = num_frames[n]);
+ *   - for every updatable component the gradient (kctc_nnet_get_grad) equal to
+ *     the SUM over n of the gradient of utterance n in a minibatch of its own,
+ * i.e. the function that kctc_nnet_propagate_seq / kctc_am_nnet_decodable_batch
+ * evaluate is the one that is trained.  It applies to kctc_nnet_train_step,
+ * kctc_nnet_train_step_async, kctc_nnet_train_simple and (their forward is
+ * then kctc_nnet_propagate_seq's) kctc_nnet_compute_objf / compute_prob.  The
+ * RNN components run krnnForwardTrainingSeq / BackwardDataSeq /
+ * BackwardWeightsSeq (kaldi_rnn.h) without the hand-overs streamed between
+ * components; the other components work row by row, unchanged.  ClipGradient's
+ * counters keep counting all T_max * N rows, padding included (a padding
+ * row's derivative is zero or dropped by the next RNN below, never clipped
+ * into a gradient).  Refused with minibatches in flight and with bf16
+ * precision set; kctc_nnet_set_precision(nnet, 1) is refused while it is on;
+ * a minibatch of more than 64 utterances fails.  Switching it off restores
+ * the default path exactly. */
+int kctc_nnet_set_length_aware(kctcNnet_t nnet, int on);
+
 /* TrainNnetSimple momentum (src/ctc/ctc-nnet-train.cc:194-245, config
  * ctc-nnet-train.h:33-66): with m != 0 every update goes to a delta copy
  * (delta += lr * clip(grad); params += delta; delta *= m) and ClipGradient

@@ -115,6 +115,41 @@ int krnnBackwardData(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq
 int krnnBackwardWeights(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length,
                         int minibatch, const float *x, const float *y, void *workspace,
                         size_t workspace_bytes, float *dw, void *reserve, size_t reserve_bytes);
+/* Length-aware training (an extension, the training half of
+ * krnnForwardInferenceSeq): the three training calls plus the HOST array
+ * seq_lengths (consumed before each call returns, no host synchronisation; the
+ * SAME lengths go to all three).  Every sequence of the padded batch is
+ * treated as if it were run alone (minibatch = 1, seq_length = len[n], same w):
+ *   y[t][n], dx[t][n]   that run's output / input gradient       (t <  len[n])
+ *   y[t][n], dx[t][n]   +0                                       (t >= len[n])
+ *   dw                  += the SUM over n of those runs' weight gradients
+ *                       (krnnBackwardWeightsSeq accumulates, like krnnBackwardWeights)
+ * Rows t >= len[n] of x and dy may hold anything finite.  A length outside
+ * [1, seq_length] (or minibatch > 64) returns KRNN_STATUS_BAD_PARAM /
+ * NOT_SUPPORTED and enqueues nothing.  The recurrences are the plain calls'
+ * launches: the reverse direction's gates and dy are shifted so that every
+ * sequence ends at the last row, its output and gate gradients are shifted
+ * back.  Sizes: krnnGetTrainingSeqWorkspaceSize / krnnGetTrainingSeqReserveSize
+ * (each at least the plain size: the reserve also keeps a masked copy of x and
+ * every stacked layer's shifted output); as with the plain calls the workspace
+ * passed to krnnBackwardWeightsSeq is the one krnnBackwardDataSeq used.
+ * Every mode at KRNN_PREC_FP32 works.  KRNN_PREC_BF16 is NOT supported here
+ * (KRNN_STATUS_NOT_SUPPORTED): its backward writes the gate gradients straight
+ * into packed bf16 GEMM operands and leaves no fp32 rows to shift back. */
+size_t krnnGetTrainingSeqWorkspaceSize(krnnDescriptor_t desc, int seq_length, int minibatch);
+size_t krnnGetTrainingSeqReserveSize(krnnDescriptor_t desc, int seq_length, int minibatch);
+int krnnForwardTrainingSeq(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length,
+                           int minibatch, const int *seq_lengths, const float *x, const float *w,
+                           float *y, void *workspace, size_t workspace_bytes, void *reserve,
+                           size_t reserve_bytes);
+int krnnBackwardDataSeq(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length,
+                        int minibatch, const int *seq_lengths, const float *y, const float *dy,
+                        const float *w, float *dx, void *workspace, size_t workspace_bytes,
+                        void *reserve, size_t reserve_bytes);
+int krnnBackwardWeightsSeq(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length,
+                           int minibatch, const int *seq_lengths, const float *x, const float *y,
+                           void *workspace, size_t workspace_bytes, float *dw, void *reserve,
+                           size_t reserve_bytes);
 /* Reads (and clears) the device error word of the persistent recurrence
  * kernels: KRNN_STATUS_TIMEOUT if a bounded spin gave up.  Synchronises. */
 int krnnGetDeviceStatus(krnnDescriptor_t desc, struct ihipStream_t *stream);

@@ -263,6 +263,45 @@ class Rnn:
                                               _ptr(workspace), workspace.numel(), _ptr(dw),
                                               _ptr(reserve), reserve.numel()), "krnnBackwardWeights")
 
+    def seq_train_sizes(self, T, N):
+        """(workspace bytes, reserve bytes) of the length-aware training calls."""
+        return (lib().krnnGetTrainingSeqWorkspaceSize(self.h, T, N), lib().krnnGetTrainingSeqReserveSize(self.h, T, N))
+
+    def _seq_lens(self, seq_lengths, N):
+        lens = np.ascontiguousarray(seq_lengths, dtype=np.int32)
+        if lens.shape != (N,):
+            raise RnnError(f"seq_lengths has shape {lens.shape}, expected ({N},)")
+        return lens
+
+    def forward_training_seq(self, x, seq_lengths, w, y, workspace, reserve, stream=None):
+        """krnnForwardTrainingSeq: as forward_inference_seq, keeping in
+        `reserve` what backward_data_seq / backward_weights_seq need
+        (workspace, reserve: seq_train_sizes(T, N) bytes; the same
+        seq_lengths go to all three calls)."""
+        T, N = x.shape[0], x.shape[1]
+        lens = self._seq_lens(seq_lengths, N)
+        _krnn_check(lib().krnnForwardTrainingSeq(self.h, _stream_handle(stream), T, N, lens.ctypes.data, _ptr(x),
+                                                 _ptr(w), _ptr(y), _ptr(workspace), workspace.numel(),
+                                                 _ptr(reserve), reserve.numel()), "krnnForwardTrainingSeq")
+
+    def backward_data_seq(self, y, dy, seq_lengths, w, dx, workspace, reserve, stream=None):
+        """krnnBackwardDataSeq: dx[:len_n, n] is the input gradient sequence n
+        gets alone, dx[len_n:, n] is 0; rows dy[len_n:, n] do not matter."""
+        T, N = y.shape[0], y.shape[1]
+        lens = self._seq_lens(seq_lengths, N)
+        _krnn_check(lib().krnnBackwardDataSeq(self.h, _stream_handle(stream), T, N, lens.ctypes.data, _ptr(y),
+                                              _ptr(dy), _ptr(w), _ptr(dx), _ptr(workspace), workspace.numel(),
+                                              _ptr(reserve), reserve.numel()), "krnnBackwardDataSeq")
+
+    def backward_weights_seq(self, x, y, seq_lengths, dw, workspace, reserve, stream=None):
+        """krnnBackwardWeightsSeq: dw += the sum over n of the weight gradient
+        of sequence n run alone."""
+        T, N = x.shape[0], x.shape[1]
+        lens = self._seq_lens(seq_lengths, N)
+        _krnn_check(lib().krnnBackwardWeightsSeq(self.h, _stream_handle(stream), T, N, lens.ctypes.data, _ptr(x),
+                                                 _ptr(y), _ptr(workspace), workspace.numel(), _ptr(dw),
+                                                 _ptr(reserve), reserve.numel()), "krnnBackwardWeightsSeq")
+
     def device_status(self, stream=None):
         return lib().krnnGetDeviceStatus(self.h, _stream_handle(stream))
 
@@ -752,6 +791,13 @@ class Nnet:
         operands, fp32 accumulation (kctc_nnet_set_precision)."""
         prec = 1 if prec in (1, "bf16") else 0
         _tcheck(lib().kctc_nnet_set_precision(self.h, prec), "set_precision")
+
+    def set_length_aware(self, on=True):
+        """kctc_nnet_set_length_aware: every utterance of a padded minibatch
+        trains (and is scored by compute_objf / compute_prob) as if it were
+        run alone; the gradient is the sum of the per-utterance gradients.
+        Off by default; at most 64 utterances, fp32-class precision only."""
+        _tcheck(lib().kctc_nnet_set_length_aware(self.h, 1 if on else 0), "set_length_aware")
 
     def set_momentum(self, m):
         _tcheck(lib().kctc_nnet_set_momentum(self.h, float(m)), "set_momentum")

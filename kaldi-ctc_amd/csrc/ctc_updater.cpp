@@ -112,6 +112,12 @@ const CuMatrixBase &NnetCtcUpdater::ForwardSeq(const float *feats, int T_max, in
       throw std::invalid_argument("ForwardSeq: num_frames[" + std::to_string(n) + "] = " +
                                   std::to_string(num_frames[n]) + " outside [1, T_max]");
   BeginStep(feats, T_max, N);
+  PropagateSeq(T_max, N, num_frames, false);
+  ThrowIfErrWord();
+  return forward_data_.back();
+}
+
+void NnetCtcUpdater::PropagateSeq(int T_max, int N, const int *num_frames, bool train) {
   const int C = nnet_->NumComponents();
   for (int c = 0; c < C; c++) {
     const Component &comp = nnet_->GetComponent(c);
@@ -125,18 +131,32 @@ const CuMatrixBase &NnetCtcUpdater::ForwardSeq(const float *feats, int T_max, in
     if (const auto *r = dynamic_cast<const CuDNNRecurrentComponent *>(&comp)) {
       // no streamed hand-over between RNNs here: it reads un-shifted images
       r->ClearPackedInput();
-      r->PropagateSeq(in, &out, num_frames);
+      if (train) {
+        r->ClearInputBound();  // (a bound a chained forward once installed: found again by the weight GEMMs' max pass)
+        r->PropagateSeqTrain(in, &out, num_frames);
+      } else {
+        r->PropagateSeq(in, &out, num_frames);
+      }
     } else {
       comp.Propagate(chunk_info_[c], chunk_info_[c + 1], in, &out);
     }
   }
-  ThrowIfErrWord();
-  return forward_data_[C];
 }
 
 void NnetCtcUpdater::Enqueue(const float *feats, int T_max, int N, const int *num_frames,
                              const int *flat_labels, const int *label_lengths) {
   if (pending_ == 2) throw std::logic_error("two minibatches already queued");
+  if (length_aware_) {  // checked before anything is set up
+    if (N > 64) throw std::invalid_argument("length-aware minibatches hold at most 64 utterances");
+    for (int n = 0; n < N && num_frames; n++)
+      if (num_frames[n] < 1 || num_frames[n] > T_max)
+        throw std::invalid_argument("length-aware minibatch: num_frames[" + std::to_string(n) + "] = " +
+                                    std::to_string(num_frames[n]) + " outside [1, T_max]");
+    for (int c = 0; c < nnet_->NumComponents(); c++)
+      if (auto *r = dynamic_cast<CuDNNRecurrentComponent *>(&nnet_->GetComponent(c)))
+        if (r->Desc().prec != 0)
+          throw std::invalid_argument("length-aware minibatches need fp32-class precision (bf16 is set)");
+  }
   BeginStep(feats, T_max, N);
   const int C = nnet_->NumComponents();
   const long rows = (long)T_max * N;
@@ -145,7 +165,8 @@ void NnetCtcUpdater::Enqueue(const float *feats, int T_max, int N, const int *nu
     KCTC_HIP_CHECK(hipStreamSynchronize(S()));  // the source is a member that is reset next
     inject_err_ = 0;
   }
-  Propagate(T_max, N);
+  if (length_aware_) PropagateSeq(T_max, N, num_frames, update_);
+  else Propagate(T_max, N);
 
   // ---- ComputeObjfAndDeriv (:171-259) with the warp-ctc ABI ----
   const CuMatrixBase &out = forward_data_[C];

@@ -317,6 +317,14 @@ class CuDNNRecurrentComponent : public UpdatableComponent {
   // sequences have host lengths num_frames[n]; out's padding rows are 0.  No
   // chaining, no packed input, no prepacks; leaves no Backprop state.
   void PropagateSeq(const CuMatrixBase &in, CuMatrixBase *out, const int *num_frames) const;
+  // Length-aware training forward (rnn.h rnn_forward_training_seq): as
+  // PropagateSeq, and the next Backprop takes the length-aware backward
+  // passes with the same lengths (kept here) -- in_deriv's padding rows come
+  // out 0, out_deriv's are not read, the gradient is the sum over the
+  // sequences of what each gets alone.  Any other forward ends that state.
+  // No chaining, no packed input, no prepacks, no streamed dx or weight
+  // gradients; the weight GEMMs still run on the side stream.
+  void PropagateSeqTrain(const CuMatrixBase &in, CuMatrixBase *out, const int *num_frames) const;
   // bf16 one-layer bidirectional components write their output also as the
   // packed bf16 GEMM operands (rnn.h rnn_packed_output); the next RNN reads
   // them instead of packing its input (set by the updater from the RNN below,
@@ -341,6 +349,9 @@ class CuDNNRecurrentComponent : public UpdatableComponent {
   float param_stddev_ = 0.02f, bias_stddev_ = 0.2f, clip_gradient_ = 5.0f;
   DevBuf params_, grad_;
   mutable DevBuf reserve_, workspace_, seq_buf_;
+  mutable std::vector<int> seq_lens_;  // PropagateSeqTrain's lengths (empty: the last forward was another one)
+  void BackpropSeq(const CuMatrixBase &in_value, const CuMatrixBase &out_value, const CuMatrixBase &out_deriv,
+                   Component *to_update_in, CuMatrixBase *in_deriv) const;
   mutable int mini_batch_ = 0, seq_length_ = 0;
   mutable bool input_projected_ = false;  // set by the previous component's PropagateChained
   mutable float input_bound_ = 0.f;       // ditto: bound on |input| (0: unknown)
@@ -605,6 +616,21 @@ class NnetCtcUpdater {
   int Pending() const { return pending_; }
   MinibatchStats Finish();
   void SetExchange(GradExchange *ex) { exchange_ = ex; }
+  // Length-aware minibatches (off by default): every utterance of a padded
+  // minibatch as if it were run alone -- costs and best paths on its real
+  // rows, and for every updatable component the SUM over the utterances of
+  // the gradient each gets in a minibatch of its own (N = 1, T =
+  // num_frames[n]).  The RNN components take PropagateSeqTrain (an updater
+  // that does not update: PropagateSeq) and the matching Backprop; the other
+  // components work row by row, unchanged: whatever they leave on the
+  // padding rows of a derivative is dropped by the next RNN's dy mask, and the
+  // CTC derivative is zero there.  ClipGradient's counters keep counting all
+  // T_max * N rows.  At most 64 utterances; fp32-class precision only.
+  void SetLengthAware(bool on) {
+    if (pending_) throw std::logic_error("the length-aware mode changed with queued minibatches (Finish them first)");
+    length_aware_ = on;
+  }
+  bool LengthAware() const { return length_aware_; }
   // NnetComputation (src/nnet2/nnet-compute.cc): forward only, N sequences
   // time-major; the output stays valid until the next minibatch
   const CuMatrixBase &Forward(const float *feats, int T_max, int N);
@@ -639,9 +665,13 @@ class NnetCtcUpdater {
   void ThrowIfErrWord();  // synchronous read-back of the step's error word
   void SetupChunks(int T_max, int N);
   void Propagate(int T, int N);
+  // ForwardSeq's and the length-aware minibatches' forward; train: the RNNs
+  // keep what their Backprop needs
+  void PropagateSeq(int T, int N, const int *num_frames, bool train);
   void Backprop(int T, int N);
   Nnet *nnet_;
   bool update_;
+  bool length_aware_ = false;
   GradExchange *exchange_ = nullptr;
   GlibcRand repair_rng_{0};
   std::vector<CuMatrix> forward_data_;

@@ -326,6 +326,8 @@ int kctc_nnet_set_precision(kctcNnet_t n, int precision) {
   return kctc_guarded([&] {
     KCTC_REQUIRE(n && (precision == 0 || precision == 1), "kctc_nnet_set_precision: precision must be 0 or 1");
     KCTC_REQUIRE(n->trainer.Pending() == 0, "kctc_nnet_set_precision with minibatches in flight");
+    KCTC_REQUIRE(precision == 0 || !n->trainer.LengthAware(),
+                 "kctc_nnet_set_precision: bf16 has no length-aware training (kctc_nnet_set_length_aware is on)");
     for (int c = 0; c < n->nnet.NumComponents(); c++)
       if (auto *r = dynamic_cast<kctc::nnet2::CuDNNRecurrentComponent *>(&n->nnet.GetComponent(c)))
         r->SetPrecision(precision);

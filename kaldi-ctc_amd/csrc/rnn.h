@@ -192,6 +192,43 @@ size_t rnn_seq_buffer_bytes(const RnnDesc &d, int T, int N);
 int rnn_forward_inference_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *x,
                               const float *w, float *y, void *workspace, size_t ws_bytes, void *reserve,
                               size_t res_bytes, void *seq_buffer, size_t seq_bytes, unsigned *err);
+// Length-aware training: the three passes with the semantics above, so that
+//   y[:len[n], n], dx[:len[n], n]  are what sequence n gets run alone (N = 1, T = len[n]),
+//   dw                            accumulates the SUM over n of those runs' gradients,
+//   y and dx rows t >= len[n]     are +0 (rows t >= len[n] of x and dy may hold anything finite).
+// The recurrence kernels are unchanged.  Forward: as the inference call, and
+// every stacked layer's output is kept in the shifted frame for the backward
+// recurrence.  Backward data: dy enters aligned like G (forward columns
+// masked, reverse columns shifted right; seq_align_dy); with dh = dc = 0
+// entering a padding step and dy = 0 on it every cell's backward yields zero
+// gate gradients and passes zero on; the recurrence writes its dGates images
+// into scratch and one launch shifts them back into the reserve
+// (seq_unalign_dgates), where the dx GEMM and the weight GEMMs read them as
+// ever.  Backward weights: un-shifted images only -- E / DX, the caller's y,
+// the masked copy of x in the reserve -- since both E and y are zero on
+// padding rows the one-step pairing of dR stays right (the shifted y holds
+// whatever the recurrence computed on padding rows: unbounded for RELU).
+// The same seq_lengths go to all three calls.  None of the streamed
+// hand-overs is used (RnnFwdChain, in_rows, RnnPrepack, the streamed dx GEMM,
+// RnnWgradStream): they read un-shifted step images.  fp32-class precision
+// only: a bf16 descriptor returns KRNN_NOT_SUPPORTED (its backward writes the
+// dGates packed, there are no fp32 rows to un-shift).  Workspace and reserve:
+// rnn_seq_train_workspace_bytes / rnn_seq_train_reserve_bytes; the workspace
+// must be the same from rnn_backward_data_seq to rnn_backward_weights_seq, as
+// for the plain calls.
+size_t rnn_seq_train_workspace_bytes(const RnnDesc &d, int T, int N);
+size_t rnn_seq_train_reserve_bytes(const RnnDesc &d, int T, int N);
+int rnn_forward_training_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *x,
+                             const float *w, float *y, void *workspace, size_t ws_bytes, void *reserve,
+                             size_t res_bytes, unsigned *err);
+int rnn_backward_data_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *y,
+                          const float *dy, const float *w, float *dx, void *workspace, size_t ws_bytes,
+                          void *reserve, size_t res_bytes, unsigned *err);
+struct RnnWgradOpts;
+// (of o: max_blocks, in_bound, s2 and beside; in_cols and pre are not used)
+int rnn_backward_weights_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *x,
+                             const float *y, void *workspace, size_t ws_bytes, float *dw, void *reserve,
+                             size_t res_bytes, const RnnWgradOpts &o);
 // bf16 one-layer bidirectional components: the forward recurrence also writes
 // its output as packed bf16 rows [T*N][2H] and columns [2H][kbt64] into the
 // reserve (the GEMM operands the next component's projection / dW and this

@@ -15,9 +15,11 @@
 //                    (launch_chain_proj / _rows), the dx GEMM
 //                    (launch_bwd_stream), the chunked weight gradients
 //                    (launch_wgrad_stream)
-//   rnn_fwd.hip      rnn_forward_training, rnn_forward_inference_seq
-//   rnn_bwd_data.hip rnn_backward_data
-//   rnn_wgrad.hip    rnn_backward_weights
+//   rnn_fwd.hip      rnn_forward_training, rnn_forward_inference_seq,
+//                    rnn_forward_training_seq (and the length-aware
+//                    training's buffer layout, SeqTrainLay)
+//   rnn_bwd_data.hip rnn_backward_data, rnn_backward_data_seq
+//   rnn_wgrad.hip    rnn_backward_weights, rnn_backward_weights_seq
 //   rnn_host.h       the declarations these units share
 // Which recurrence runs and where the workspace's parts lie: rnn_plan.hip
 // (plan_rec, RnnWs); what may run beside a recurrence: rec_gate.hip; the

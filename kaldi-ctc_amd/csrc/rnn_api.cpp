@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <exception>
 #include <new>
 
@@ -177,6 +178,54 @@ int krnnBackwardWeights(krnnDescriptor_t desc, struct ihipStream_t *stream, int 
   try {
     return kctc::rnn_backward_weights(desc->desc, stream, seq_length, minibatch, x, y, workspace,
                                       workspace_bytes, dw, reserve, reserve_bytes);
+  } catch (...) {
+    return KRNN_STATUS_EXECUTION_FAILED;
+  }
+}
+
+size_t krnnGetTrainingSeqWorkspaceSize(krnnDescriptor_t desc, int seq_length, int minibatch) {
+  if (!desc || seq_length <= 0 || minibatch <= 0) return 0;
+  // (never below krnnGetWorkspaceSize: one buffer sized by this query serves the plain calls too)
+  return std::max(kctc::rnn_seq_train_workspace_bytes(desc->desc, seq_length, minibatch),
+                  krnnGetWorkspaceSize(desc, seq_length, minibatch));
+}
+
+size_t krnnGetTrainingSeqReserveSize(krnnDescriptor_t desc, int seq_length, int minibatch) {
+  if (!desc || seq_length <= 0 || minibatch <= 0) return 0;
+  return kctc::rnn_seq_train_reserve_bytes(desc->desc, seq_length, minibatch);
+}
+
+int krnnForwardTrainingSeq(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length, int minibatch,
+                           const int *seq_lengths, const float *x, const float *w, float *y, void *workspace,
+                           size_t workspace_bytes, void *reserve, size_t reserve_bytes) {
+  if (!desc || !seq_lengths || !x || !w || !y || !workspace || !reserve) return KRNN_STATUS_BAD_PARAM;
+  try {
+    return kctc::rnn_forward_training_seq(desc->desc, stream, seq_length, minibatch, seq_lengths, x, w, y, workspace,
+                                          workspace_bytes, reserve, reserve_bytes, desc->dev_err());
+  } catch (...) {
+    return KRNN_STATUS_EXECUTION_FAILED;
+  }
+}
+
+int krnnBackwardDataSeq(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length, int minibatch,
+                        const int *seq_lengths, const float *y, const float *dy, const float *w, float *dx,
+                        void *workspace, size_t workspace_bytes, void *reserve, size_t reserve_bytes) {
+  if (!desc || !seq_lengths || !y || !dy || !w || !workspace || !reserve) return KRNN_STATUS_BAD_PARAM;
+  try {
+    return kctc::rnn_backward_data_seq(desc->desc, stream, seq_length, minibatch, seq_lengths, y, dy, w, dx,
+                                       workspace, workspace_bytes, reserve, reserve_bytes, desc->dev_err());
+  } catch (...) {
+    return KRNN_STATUS_EXECUTION_FAILED;
+  }
+}
+
+int krnnBackwardWeightsSeq(krnnDescriptor_t desc, struct ihipStream_t *stream, int seq_length, int minibatch,
+                           const int *seq_lengths, const float *x, const float *y, void *workspace,
+                           size_t workspace_bytes, float *dw, void *reserve, size_t reserve_bytes) {
+  if (!desc || !seq_lengths || !x || !y || !dw || !reserve || !workspace) return KRNN_STATUS_BAD_PARAM;
+  try {
+    return kctc::rnn_backward_weights_seq(desc->desc, stream, seq_length, minibatch, seq_lengths, x, y, workspace,
+                                          workspace_bytes, dw, reserve, reserve_bytes, kctc::RnnWgradOpts{});
   } catch (...) {
     return KRNN_STATUS_EXECUTION_FAILED;
   }

@@ -1,6 +1,7 @@
 // rnn_bwd_data.hip -- the RNN host's backward-data pass (map of the units:
 // rnn.hip): rnn_backward_data, dGates into the reserve and dx.
 #include "rnn_host.h"
+#include "seq_align.h"
 
 namespace kctc {
 namespace {
@@ -99,19 +100,22 @@ void dx_gemm(const RnnDesc &d, const RnnWs &ws, hipStream_t s, long TN, int l, c
     }
   }
 }
-}  // namespace
+// Length-aware (rnn_backward_data_seq): the lengths and where the shifted
+// images lie -- ysh (+ l * ysh_layer): layer l's output as the forward
+// recurrence wrote it; dya: dy aligned; es / xs: E / DX (a GRU's) as the
+// backward recurrence writes them
+struct SeqBwd {
+  SeqLens lens;
+  const float *ysh;
+  long ysh_layer;
+  float *dya, *es, *xs;
+};
 
-int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float *y,
-                      const float *dy, const float *w, float *dx, void *workspace,
-                      size_t ws_bytes, void *reserve, size_t res_bytes, unsigned *err,
-                      hipStream_t overlap, RnnWgradStream *wgrad, const RnnPrepack *pre) {
+// The layers of a backward-data pass; seq null: rnn_backward_data's
+int backward_layers(const RnnDesc &d, hipStream_t s, int T, int N, const float *y, const float *dy, const float *w,
+                    float *dx, RnnCall &c, void *reserve, unsigned *err, hipStream_t overlap, RnnWgradStream *wgrad,
+                    const RnnPrepack *pre, const SeqBwd *seq) {
   RecScope rec_scope;  // the side launches' residency gates (beside_recurrence)
-  if (wgrad) wgrad->done = false;
-  if (!range_ok(d, T, N)) return KRNN_NOT_SUPPORTED;
-  RnnCall c(d, T, N, workspace);
-  if (!c.reserve_fits(res_bytes)) return KRNN_BAD_PARAM;
-  if (!c.plan(false)) return KRNN_NOT_SUPPORTED;  // (before the workspace check, unlike the forward)
-  if (!c.workspace_fits(ws_bytes)) return KRNN_BAD_PARAM;
   const RnnReserveLayout &lay = c.lay; const RnnWs &ws = c.ws; const RecPlan &pl = c.pl;
   const bool v6 = pl.ver == 6;
   const long TN = (long)T * N;
@@ -124,16 +128,22 @@ int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float
     const float *wl = w + lw.pl0;
     float *E = R0 + lay.E;
     float *DX = d.mode == kGru ? R0 + lay.DX : E;
+    if (seq) {  // h and c in the shifted frame; dy aligned to it
+      out = seq->ysh + seq->ysh_layer * l;
+      seq_align_dy(s, dcur, seq->dya, T, N, d.dirs * d.H, d.H, seq->lens);
+      dcur = seq->dya;
+    }
+    float *Er = seq ? seq->es : E, *DXr = seq ? (d.mode == kGru ? seq->xs : seq->es) : DX;
     RecParams p = rec_params(d, pl, ws, T, N, wl, lw, R0, lay, const_cast<float *>(out), err, s);
     // dx_l = sum_dir DX_dir W_dir   (lower layer's dy, or the caller's dx)
     float *dxl = (l == 0) ? dx : res + lay.per_layer * (l - 1) + lay.dout;
     // streamed: computed on `overlap` while the recurrence runs, from its rows as they appear
-    const bool streamed = dxl && overlap && v6 && bwd_dx_stream_ok(pl, d, l, T, N);
+    const bool streamed = !seq && dxl && overlap && v6 && bwd_dx_stream_ok(pl, d, l, T, N);
     // weight gradients streamed off this recurrence (the bottom component):
     // its dGates rows must be written through too
-    const bool wstream = wgrad && wgrad->side && !dxl && v6 && !p.xpd && d.layers == 1 &&
+    const bool wstream = !seq && wgrad && wgrad->side && !dxl && v6 && !p.xpd && d.layers == 1 &&
                          wgrad_stream_shape(d, T, N) && wgrad_stream_ok(pl, d, T, N);
-    bwd_rec_params(p, d, pl, ws, R0, lay, dcur, E, DX, streamed || wstream, s);
+    bwd_rec_params(p, d, pl, ws, R0, lay, dcur, Er, DXr, streamed || wstream, s);
     const hipEvent_t fork = (streamed || wstream) ? fork_event(s) : nullptr;
     RegWord &rw = reg_of_device();
     if (v6) p.reg = rw.word;  // registration for the exchange's residency gate
@@ -149,10 +159,45 @@ int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float
     if (wstream) launch_wgrad_stream(pl, d, live(p), fork, T, N, y, ws, reserve, err, *wgrad, s);
     if (v6) xch_release(s);
     tr.dump("bwd", s, pl.grid, p.nwg, T, d.dirs, pl.ver, p.xpd);
+    // the dGates images back into the un-shifted frame, padding rows +0 (the
+    // recurrence leaves denormals there when its hand-off tags the payload
+    // words): what the dx GEMM here and the weight GEMMs later read
+    if (seq) seq_unalign_dgates(s, Er, E, DXr, DX, T, N, d.dirs * d.nw() * d.H, d.nw() * d.H, seq->lens);
     if (dxl && !streamed) dx_gemm(d, ws, s, TN, l, DX, p.dxr, wl, lw.pls, dxl);
     dcur = dxl;
   }
   return KRNN_OK;
+}
+}  // namespace
+
+int rnn_backward_data(const RnnDesc &d, hipStream_t s, int T, int N, const float *y,
+                      const float *dy, const float *w, float *dx, void *workspace,
+                      size_t ws_bytes, void *reserve, size_t res_bytes, unsigned *err,
+                      hipStream_t overlap, RnnWgradStream *wgrad, const RnnPrepack *pre) {
+  if (wgrad) wgrad->done = false;
+  if (!range_ok(d, T, N)) return KRNN_NOT_SUPPORTED;
+  RnnCall c(d, T, N, workspace);
+  if (!c.reserve_fits(res_bytes)) return KRNN_BAD_PARAM;
+  if (!c.plan(false)) return KRNN_NOT_SUPPORTED;  // (before the workspace check, unlike the forward)
+  if (!c.workspace_fits(ws_bytes)) return KRNN_BAD_PARAM;
+  return backward_layers(d, s, T, N, y, dy, w, dx, c, reserve, err, overlap, wgrad, pre, nullptr);
+}
+
+int rnn_backward_data_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *y,
+                          const float *dy, const float *w, float *dx, void *workspace, size_t ws_bytes,
+                          void *reserve, size_t res_bytes, unsigned *err) {
+  SeqBwd q;
+  if (int st = seq_train_entry(d, T, N, seq_lengths, ws_bytes, res_bytes, &q.lens)) return st;
+  RnnCall c(d, T, N, workspace);
+  if (!c.plan(false)) return KRNN_NOT_SUPPORTED;
+  const SeqTrainLay sl(d, T, N);
+  char *wb = static_cast<char *>(workspace), *rb = static_cast<char *>(reserve);
+  q.ysh = reinterpret_cast<const float *>(rb + sl.ysh);
+  q.ysh_layer = (long)(sl.ysh_layer / sizeof(float));
+  q.dya = reinterpret_cast<float *>(wb + sl.dy);
+  q.es = reinterpret_cast<float *>(wb + sl.g);
+  q.xs = reinterpret_cast<float *>(wb + sl.g2);
+  return backward_layers(d, s, T, N, y, dy, w, dx, c, reserve, err, nullptr, nullptr, nullptr, &q);
 }
 
 }  // namespace kctc

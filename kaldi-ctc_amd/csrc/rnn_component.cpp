@@ -106,6 +106,7 @@ void CuDNNRecurrentComponent::Forward(const CuMatrixBase &in, CuMatrixBase *out,
   if (in.NumCols() != desc_.D || in.NumRows() % N)
     throw std::invalid_argument("CuDNNRecurrentComponent::Propagate: bad input shape");
   seq_length_ = T;
+  seq_lens_.clear();
   reserve_.ensure(sizeof(float) * rnn_reserve_layout(desc_, T, N).total);
   workspace_.ensure(rnn_workspace_bytes(desc_, T, N));
   const bool projected = input_projected_;
@@ -150,6 +151,7 @@ void CuDNNRecurrentComponent::PropagateSeq(const CuMatrixBase &in, CuMatrixBase 
   seq_buf_.ensure(rnn_seq_buffer_bytes(desc_, T, N));
   // the reserve no longer holds a training forward, and nothing was streamed
   seq_length_ = 0;
+  seq_lens_.clear();
   input_projected_ = false;
   in_tn_[0] = in_tn_[1] = -1;
   pre_.done = pre_.wdone = false;
@@ -160,10 +162,66 @@ void CuDNNRecurrentComponent::PropagateSeq(const CuMatrixBase &in, CuMatrixBase 
   if (st) throw std::runtime_error("rnn_forward_inference_seq failed: " + std::to_string(st));
 }
 
+void CuDNNRecurrentComponent::PropagateSeqTrain(const CuMatrixBase &in, CuMatrixBase *out,
+                                                const int *num_frames) const {
+  const int N = mini_batch_ > 0 ? mini_batch_ : 1;
+  const int T = (int)(in.NumRows() / N);
+  if (in.NumCols() != desc_.D || in.NumRows() % N || !num_frames)
+    throw std::invalid_argument("CuDNNRecurrentComponent::PropagateSeqTrain: bad input shape");
+  reserve_.ensure(rnn_seq_train_reserve_bytes(desc_, T, N));
+  workspace_.ensure(rnn_seq_train_workspace_bytes(desc_, T, N));
+  // the reserve holds a length-aware training forward; nothing was streamed or prepacked
+  seq_length_ = T;
+  seq_lens_.assign(num_frames, num_frames + N);
+  input_projected_ = false;
+  in_tn_[0] = in_tn_[1] = -1;
+  pre_.done = pre_.wdone = false;
+  ProfScope ps("layer_rnn_forward");
+  int st = rnn_forward_training_seq(desc_, S(), T, N, num_frames, in.Data(), params_.f(), out->Data(), workspace_.p,
+                                    workspace_.bytes, reserve_.p, reserve_.bytes, DeviceError());
+  if (st) {
+    seq_lens_.clear();
+    throw std::runtime_error("rnn_forward_training_seq failed: " + std::to_string(st));
+  }
+}
+
+void CuDNNRecurrentComponent::BackpropSeq(const CuMatrixBase &in_value, const CuMatrixBase &out_value,
+                                          const CuMatrixBase &out_deriv, Component *to_update_in,
+                                          CuMatrixBase *in_deriv) const {
+  const int N = mini_batch_, T = seq_length_;
+  if ((int)seq_lens_.size() != N) throw std::logic_error("CuDNNRecurrentComponent: Backprop after another minibatch");
+  {
+    ProfScope ps("layer_rnn_backward_data");
+    int st = rnn_backward_data_seq(desc_, S(), T, N, seq_lens_.data(), out_value.Data(), out_deriv.Data(),
+                                   params_.f(), in_deriv ? in_deriv->Data() : nullptr, workspace_.p, workspace_.bytes,
+                                   reserve_.p, reserve_.bytes, DeviceError());
+    if (st) throw std::runtime_error("rnn_backward_data_seq failed: " + std::to_string(st));
+  }
+  if (!to_update_in) return;
+  auto *to_update = dynamic_cast<CuDNNRecurrentComponent *>(to_update_in);
+  if (!to_update) throw std::invalid_argument("CuDNNRecurrentComponent: bad to_update");
+  // as Backprop: on the side stream beside the next component's backward recurrence
+  auto &dev = CuDevice::Instantiate();
+  hipStream_t ws = dev.side ? dev.side : S();
+  dev.Fork();
+  to_update->grad_stream_ = ws;
+  KCTC_HIP_CHECK(hipMemsetAsync(to_update->grad_.p, 0, sizeof(float) * NumParameters(), ws));
+  ProfScope ps("layer_rnn_backward_weights", ws);
+  RnnWgradOpts o;
+  o.max_blocks = dev.side ? side_gemm_blocks() : 0; o.in_bound = input_bound_;
+  o.s2 = (!in_deriv && dev.side) ? dev.stream2 : nullptr;
+  o.beside = in_deriv && dev.side;
+  int st = rnn_backward_weights_seq(desc_, ws, T, N, seq_lens_.data(), in_value.Data(), out_value.Data(),
+                                    workspace_.p, workspace_.bytes, to_update->grad_.f(), reserve_.p, reserve_.bytes,
+                                    o);
+  if (st) throw std::runtime_error("rnn_backward_weights_seq failed: " + std::to_string(st));
+}
+
 void CuDNNRecurrentComponent::Backprop(const ChunkInfo &, const ChunkInfo &,
                                        const CuMatrixBase &in_value, const CuMatrixBase &out_value,
                                        const CuMatrixBase &out_deriv, Component *to_update_in,
                                        CuMatrixBase *in_deriv) const {
+  if (!seq_lens_.empty()) return BackpropSeq(in_value, out_value, out_deriv, to_update_in, in_deriv);
   const int N = mini_batch_, T = seq_length_;
   auto &dev0 = CuDevice::Instantiate();
   // the bottom component (no input derivative): its weight gradients are

@@ -1,5 +1,6 @@
 // rnn_fwd.hip -- the RNN host's forward passes (map of the units: rnn.hip):
-// rnn_forward_training and the length-aware rnn_forward_inference_seq.
+// rnn_forward_training and the length-aware rnn_forward_inference_seq /
+// rnn_forward_training_seq.
 #include "rnn_host.h"
 #include "seq_align.h"
 
@@ -188,32 +189,31 @@ struct SeqBuf {
 
 size_t rnn_seq_buffer_bytes(const RnnDesc &d, int T, int N) { return SeqBuf(d, T, N).total; }
 
-int rnn_forward_inference_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *x,
-                              const float *w, float *y, void *workspace, size_t ws_bytes, void *reserve,
-                              size_t res_bytes, void *seq_buffer, size_t seq_bytes, unsigned *err) {
+namespace {
+// What the length-aware forwards share.  xz: the layer-0 input with its
+// padding zeroed; gs: one layer's projected G before the shift; ys: the
+// recurrence's output before the shift back -- one image reused by every
+// stacked layer (ys_layer 0: inference) or one per layer, ys_layer floats
+// apart, kept for the backward recurrence (training).
+int forward_seq(const RnnDesc &d, hipStream_t s, int T, int N, const SeqLens &lens, bool train, const float *x,
+                const float *w, float *y, RnnCall &c, void *reserve, float *xz, float *gs, float *ys, long ys_layer,
+                unsigned *err) {
   RecScope rec_scope;
-  if (!range_ok(d, T, N)) return KRNN_NOT_SUPPORTED;
-  SeqLens lens;
-  if (!seq_lens(seq_lengths, T, N, &lens)) return KRNN_BAD_PARAM;
-  RnnCall c(d, T, N, workspace);
-  if (!c.reserve_fits(res_bytes) || !c.workspace_fits(ws_bytes)) return KRNN_BAD_PARAM;
-  const SeqBuf sb(d, T, N);
-  if (!seq_buffer || seq_bytes < sb.total) return KRNN_BAD_PARAM;
-  if (!c.plan(true)) return KRNN_NOT_SUPPORTED;
   const RnnReserveLayout &lay = c.lay; const RnnWs &ws = c.ws; const RecPlan &pl = c.pl;
   const int H = d.H, dirs = d.dirs, NW = d.nw();
   const long TN = (long)T * N;
-  char *sbase = static_cast<char *>(seq_buffer);
-  float *xz = reinterpret_cast<float *>(sbase + sb.xz), *gs = reinterpret_cast<float *>(sbase + sb.g),
-        *ys = reinterpret_cast<float *>(sbase + sb.y);
   float *res = static_cast<float *>(reserve);
+  // (the training passes: the same maps under profile names of their own)
+  const auto align = train ? seq_align_train : seq_align;
+  const auto unalign = train ? seq_unalign_train : seq_unalign;
   // padding rows of the input may hold anything: zeroed before the projection
-  seq_align(s, x, xz, T, N, d.D, d.D, lens);
+  align(s, x, xz, T, N, d.D, d.D, lens);
   const float *in = xz;
   for (int l = 0; l < d.layers; l++) {
     const bool last = l == d.layers - 1;
     float *R0 = res + lay.per_layer * l;
     float *out = last ? y : R0 + lay.out;
+    float *ysl = ys + ys_layer * l;
     const LayerW lw = layer_w(d, l);
     const float *wl = w + lw.pl0;
     // no streamed hand-over and no packed input rows here: they read
@@ -222,20 +222,83 @@ int rnn_forward_inference_seq(const RnnDesc &d, hipStream_t s, int T, int N, con
       // the reverse direction's gate columns move right by T - len[n] frames,
       // so that every sequence ends at row T-1 where that recurrence starts
       project_input(d, ws, s, TN, l, in, nullptr, wl, lw, gs);
-      seq_align(s, gs, R0 + lay.G, T, N, dirs * NW * H, NW * H, lens);
+      align(s, gs, R0 + lay.G, T, N, dirs * NW * H, NW * H, lens);
     } else {
       project_input(d, ws, s, TN, l, in, nullptr, wl, lw, R0 + lay.G);
     }
-    RecParams p = rec_params(d, pl, ws, T, N, wl, lw, R0, lay, ys, err, s);
+    RecParams p = rec_params(d, pl, ws, T, N, wl, lw, R0, lay, ysl, err, s);
     fwd_rec_params(p, d, pl, ws, R0, lay, false, false, s);
     RecTrace tr;
     launch_planned(d, pl, true, p, tr, rec_scope, s);
     tr.dump("fwd", s, pl.grid, p.nwg, T, dirs, pl.ver, p.xpd);
     // ... and its output moves back; padding rows of both directions become 0
-    seq_unalign(s, ys, out, T, N, dirs * H, H, lens);
+    unalign(s, ysl, out, T, N, dirs * H, H, lens);
     in = out;
   }
   return KRNN_OK;
+}
+}  // namespace
+
+int rnn_forward_inference_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *x,
+                              const float *w, float *y, void *workspace, size_t ws_bytes, void *reserve,
+                              size_t res_bytes, void *seq_buffer, size_t seq_bytes, unsigned *err) {
+  if (!range_ok(d, T, N)) return KRNN_NOT_SUPPORTED;
+  SeqLens lens;
+  if (!seq_lens(seq_lengths, T, N, &lens)) return KRNN_BAD_PARAM;
+  RnnCall c(d, T, N, workspace);
+  if (!c.reserve_fits(res_bytes) || !c.workspace_fits(ws_bytes)) return KRNN_BAD_PARAM;
+  const SeqBuf sb(d, T, N);
+  if (!seq_buffer || seq_bytes < sb.total) return KRNN_BAD_PARAM;
+  if (!c.plan(true)) return KRNN_NOT_SUPPORTED;
+  char *sbase = static_cast<char *>(seq_buffer);
+  return forward_seq(d, s, T, N, lens, false, x, w, y, c, reserve, reinterpret_cast<float *>(sbase + sb.xz),
+                     reinterpret_cast<float *>(sbase + sb.g), reinterpret_cast<float *>(sbase + sb.y), 0, err);
+}
+
+// ---------------------------------------------------------------------------
+// length-aware training (rnn.h rnn_forward_training_seq)
+// ---------------------------------------------------------------------------
+SeqTrainLay::SeqTrainLay(const RnnDesc &d, int T, int N) {
+  const size_t TN = (size_t)T * N;
+  const size_t gates = align_up(sizeof(float) * TN * d.dirs * d.nw() * d.H, 256);
+  const size_t outs = align_up(sizeof(float) * TN * d.dirs * d.H, 256);
+  ws0 = align_up(rnn_workspace_bytes(d, T, N), 256);
+  g = ws0;
+  g2 = g + gates;
+  dy = g2 + (d.mode == kGru ? gates : 0);
+  ws_total = dy + outs;
+  res0 = align_up(sizeof(float) * (size_t)rnn_reserve_layout(d, T, N).total, 256);
+  xz = res0;
+  ysh = xz + align_up(sizeof(float) * TN * d.D, 256);
+  ysh_layer = outs;
+  res_total = ysh + outs * d.layers;
+}
+
+size_t rnn_seq_train_workspace_bytes(const RnnDesc &d, int T, int N) { return SeqTrainLay(d, T, N).ws_total; }
+size_t rnn_seq_train_reserve_bytes(const RnnDesc &d, int T, int N) { return SeqTrainLay(d, T, N).res_total; }
+
+int seq_train_entry(const RnnDesc &d, int T, int N, const int *seq_lengths, size_t ws_bytes, size_t res_bytes,
+                    SeqLens *lens) {
+  if (!range_ok(d, T, N)) return KRNN_NOT_SUPPORTED;
+  if (d.prec == kPrecBf16) return KRNN_NOT_SUPPORTED;  // its direct path leaves no fp32 dGates rows to un-shift
+  if (!seq_lens(seq_lengths, T, N, lens)) return KRNN_BAD_PARAM;
+  const SeqTrainLay sl(d, T, N);
+  if (ws_bytes < sl.ws_total || res_bytes < sl.res_total) return KRNN_BAD_PARAM;
+  return KRNN_OK;
+}
+
+int rnn_forward_training_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *x,
+                             const float *w, float *y, void *workspace, size_t ws_bytes, void *reserve,
+                             size_t res_bytes, unsigned *err) {
+  SeqLens lens;
+  if (int st = seq_train_entry(d, T, N, seq_lengths, ws_bytes, res_bytes, &lens)) return st;
+  RnnCall c(d, T, N, workspace);
+  if (!c.plan(true)) return KRNN_NOT_SUPPORTED;
+  const SeqTrainLay sl(d, T, N);
+  char *wb = static_cast<char *>(workspace), *rb = static_cast<char *>(reserve);
+  return forward_seq(d, s, T, N, lens, true, x, w, y, c, reserve, reinterpret_cast<float *>(rb + sl.xz),
+                     reinterpret_cast<float *>(wb + sl.g), reinterpret_cast<float *>(rb + sl.ysh),
+                     (long)(sl.ysh_layer / sizeof(float)), err);
 }
 
 }  // namespace kctc

@@ -170,6 +170,26 @@ void launch_wgrad_stream(const RecPlan &pl, const RnnDesc &d, const RecLive &p, 
                          const float *y, const RnnWs &ws, void *reserve, unsigned *err, RnnWgradStream &wgrad,
                          hipStream_t s);
 
+// ---- rnn_fwd.hip: where the length-aware training passes keep their images ----
+// Byte offsets.  Workspace: [rnn_workspace_bytes | g: G before the shift, then
+// the backward's E before the shift back | g2: a GRU's DX likewise | dy: one
+// layer's aligned dy].  Reserve: [rnn_reserve_layout | xz: the input with its
+// padding zeroed (the weight GEMMs read it) | ysh: every stacked layer's
+// output in the shifted frame, ysh_layer apart (the backward recurrence reads
+// h and c there)].  Unidirectional: G is projected in place, but the dGates
+// still pass through g / g2: a v6 hand-off that tags its payload words leaves
+// denormals where the padding steps' gradients are zero in exact arithmetic,
+// and the pass back writes those rows as +0.
+struct SeqTrainLay {
+  size_t ws0, g, g2, dy, ws_total;
+  size_t res0, xz, ysh, ysh_layer, res_total;
+  SeqTrainLay(const RnnDesc &d, int T, int N);
+};
+// The checks the three length-aware training entries share (KRNN_OK: lens is set)
+struct SeqLens;
+int seq_train_entry(const RnnDesc &d, int T, int N, const int *seq_lengths, size_t ws_bytes, size_t res_bytes,
+                    SeqLens *lens);
+
 // ---- rnn_wgrad.hip: what the weight-gradient stream launches per chunk --------
 void wgrad_frames(const RnnDesc &d, hipStream_t s, int T, int N, const float *x, const float *y, const RnnWs &ws,
                   float *dw, void *reserve, int max_blocks, float in_bound, int dir, int ta, int tb);

@@ -3,6 +3,7 @@
 // cudnnRNNBackwardWeights), and the per-chunk products and bias sums of the
 // weight-gradient stream (rnn_stream.hip launch_wgrad_stream).
 #include "rnn_host.h"
+#include "seq_align.h"
 
 namespace kctc {
 namespace {
@@ -360,6 +361,22 @@ int rnn_backward_weights(const RnnDesc &d, hipStream_t s, int T, int N, const fl
     wgrad_bias(c.pl, d, s, T, N, dw, reserve, l);
   }
   return KRNN_OK;
+}
+
+// Length-aware: the plain pass on the un-shifted images -- the dGates that
+// rnn_backward_data_seq shifted back, the caller's y and the reserve's copy of
+// x, all zero on padding rows -- without the forward's prepacks or packed input
+int rnn_backward_weights_seq(const RnnDesc &d, hipStream_t s, int T, int N, const int *seq_lengths, const float *x,
+                             const float *y, void *workspace, size_t ws_bytes, float *dw, void *reserve,
+                             size_t res_bytes, const RnnWgradOpts &o) {
+  (void)x;  // its masked copy is read instead: the caller's padding rows may hold anything
+  SeqLens lens;
+  if (int st = seq_train_entry(d, T, N, seq_lengths, ws_bytes, res_bytes, &lens)) return st;
+  const SeqTrainLay sl(d, T, N);
+  RnnWgradOpts po = o;
+  po.in_cols = nullptr; po.pre = nullptr;
+  return rnn_backward_weights(d, s, T, N, reinterpret_cast<const float *>(static_cast<char *>(reserve) + sl.xz), y,
+                              workspace, sl.ws0, dw, reserve, sl.res0, po);
 }
 
 }  // namespace kctc

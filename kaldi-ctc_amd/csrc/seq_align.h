@@ -28,6 +28,20 @@ bool seq_lens(const int *host_lens, int T, int N, SeqLens *out);
 // Rows t >= len[n] of src are never read by seq_align.
 void seq_align(hipStream_t s, const float *src, float *dst, int T, int N, int W, int Wfwd, const SeqLens &lens);
 void seq_unalign(hipStream_t s, const float *src, float *dst, int T, int N, int W, int Wfwd, const SeqLens &lens);
+// The passes of length-aware training, the same two maps under profile names
+// of their own and a grid capped at 8 blocks per CU (grid-stride beyond):
+//   seq_align_train / seq_unalign_train  G in, y out of the forward
+//   seq_align_dy        dy into the backward recurrence (padding rows of dy
+//                       may hold anything finite: never read)
+//   seq_unalign_dgates  the backward recurrence's dGates images out of their
+//                       scratch: E and (a GRU; else null or == e_src) DX, both
+//                       [T*N][W], in ONE launch; padding rows become +0
+void seq_align_train(hipStream_t s, const float *src, float *dst, int T, int N, int W, int Wfwd, const SeqLens &lens);
+void seq_unalign_train(hipStream_t s, const float *src, float *dst, int T, int N, int W, int Wfwd,
+                       const SeqLens &lens);
+void seq_align_dy(hipStream_t s, const float *dy, float *dst, int T, int N, int W, int Wfwd, const SeqLens &lens);
+void seq_unalign_dgates(hipStream_t s, const float *e_src, float *e_dst, const float *dx_src, float *dx_dst, int T,
+                        int N, int W, int Wfwd, const SeqLens &lens);
 
 // CtcDecodableAmNnet over a batch: probs [T*N][A] time-major (the output of a
 // model ending in SoftmaxComponent), utterance n has frames t < len[n].  The

@@ -1,4 +1,4 @@
-// seq_align.hip -- the kernels of the length-aware inference path (gfx950).
+// seq_align.hip -- the kernels of the length-aware inference and training paths (gfx950).
 //
 // A batch of N sequences of lengths len[n] <= T runs through the unchanged
 // persistent recurrences, which know nothing of lengths.  The forward
@@ -8,7 +8,10 @@
 // direction's columns) are shifted right by T - len[n] frames before the
 // recurrence, and that direction's output is shifted back after it
 // (k_seq_shift, one pass each, 16-byte accesses, no atomics).  Padding rows
-// are written as zeros on both sides.
+// are written as zeros on both sides.  Training (rnn.h rnn_forward_training_seq)
+// uses the same map twice more: dy enters the backward recurrence aligned like
+// G (forward columns masked, reverse columns shifted right), and the dGates
+// images E / DX leave it un-aligned like y, both in one launch.
 //
 // Decode side: k_blank_scan_batch / k_decodable_rows_batch build the
 // CtcDecodableAmNnet matrix (decodable.hip has the arithmetic) of N utterances
@@ -39,12 +42,16 @@ namespace {
 
 // V: float4 (W, Wfwd multiples of 4, 16-byte aligned buffers) or float.
 // One element of V per thread and grid-stride step; Wv / Wfv in units of V.
+// blockIdx.y picks the image: (src, dst) or, one launch for two images of the
+// same shape (a GRU's E and DX), (src2, dst2).
 template <typename V, bool kUnalign>
-__global__ __launch_bounds__(256) void k_seq_shift(const V *__restrict__ src, V *__restrict__ dst, int T, int N, int Wv,
-                                                   int Wfv, SeqLens lens, long total) {
+__global__ __launch_bounds__(256) void k_seq_shift(const V *__restrict__ src, V *__restrict__ dst,
+                                                   const V *__restrict__ src2, V *__restrict__ dst2, int T, int N,
+                                                   int Wv, int Wfv, SeqLens lens, long total) {
   __shared__ int sl[kSeqMaxN];
   if (threadIdx.x < kSeqMaxN) sl[threadIdx.x] = lens.len[threadIdx.x];
   __syncthreads();
+  if (blockIdx.y) { src = src2; dst = dst2; }
   const long step = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += step) {
     const long row = i / Wv;
@@ -65,21 +72,30 @@ __global__ __launch_bounds__(256) void k_seq_shift(const V *__restrict__ src, V 
   }
 }
 
+// The training passes (tag given) cap the grid at 8 blocks per CU and
+// grid-stride the rest; the inference passes keep their launch.
+constexpr long kTrainGridCap = 2048;
+
 template <bool kUnalign>
-void launch_shift(hipStream_t s, const float *src, float *dst, int T, int N, int W, int Wfwd, const SeqLens &lens) {
+void launch_shift(hipStream_t s, const float *src, float *dst, int T, int N, int W, int Wfwd, const SeqLens &lens,
+                  const char *tag = nullptr, const float *src2 = nullptr, float *dst2 = nullptr) {
   if (T <= 0 || N <= 0 || W <= 0) return;
-  const bool v4 = W % 4 == 0 && Wfwd % 4 == 0 && ((uintptr_t)src | (uintptr_t)dst) % 16 == 0;
+  const bool two = src2 && dst2;
+  uintptr_t bits = (uintptr_t)src | (uintptr_t)dst;
+  if (two) bits |= (uintptr_t)src2 | (uintptr_t)dst2;
+  const bool v4 = W % 4 == 0 && Wfwd % 4 == 0 && bits % 16 == 0;
   const int e = v4 ? 4 : 1;
   const long total = (long)T * N * (W / e);
-  const unsigned grid = (unsigned)std::min<long>((total + 255) / 256, 1L << 16);
-  ProfSpan ps(s, kUnalign ? "seq_unalign" : "seq_align");
+  const unsigned grid = (unsigned)std::min<long>((total + 255) / 256, tag ? kTrainGridCap : 1L << 16);
+  ProfSpan ps(s, tag ? tag : kUnalign ? "seq_unalign" : "seq_align");
   if (v4)
-    hipLaunchKernelGGL((k_seq_shift<float4, kUnalign>), dim3(grid), dim3(256), 0, s,
-                       reinterpret_cast<const float4 *>(src), reinterpret_cast<float4 *>(dst), T, N, W / 4, Wfwd / 4,
-                       lens, total);
+    hipLaunchKernelGGL((k_seq_shift<float4, kUnalign>), dim3(grid, two ? 2 : 1), dim3(256), 0, s,
+                       reinterpret_cast<const float4 *>(src), reinterpret_cast<float4 *>(dst),
+                       reinterpret_cast<const float4 *>(src2), reinterpret_cast<float4 *>(dst2), T, N, W / 4,
+                       Wfwd / 4, lens, total);
   else
-    hipLaunchKernelGGL((k_seq_shift<float, kUnalign>), dim3(grid), dim3(256), 0, s, src, dst, T, N, W, Wfwd, lens,
-                       total);
+    hipLaunchKernelGGL((k_seq_shift<float, kUnalign>), dim3(grid, two ? 2 : 1), dim3(256), 0, s, src, dst, src2, dst2,
+                       T, N, W, Wfwd, lens, total);
   KCTC_HIP_CHECK(hipGetLastError());
 }
 
@@ -185,6 +201,24 @@ void seq_align(hipStream_t s, const float *src, float *dst, int T, int N, int W,
 }
 void seq_unalign(hipStream_t s, const float *src, float *dst, int T, int N, int W, int Wfwd, const SeqLens &lens) {
   launch_shift<true>(s, src, dst, T, N, W, Wfwd, lens);
+}
+
+void seq_align_dy(hipStream_t s, const float *dy, float *dst, int T, int N, int W, int Wfwd, const SeqLens &lens) {
+  launch_shift<false>(s, dy, dst, T, N, W, Wfwd, lens, "seq_align_dy");
+}
+void seq_unalign_dgates(hipStream_t s, const float *e_src, float *e_dst, const float *dx_src, float *dx_dst, int T,
+                        int N, int W, int Wfwd, const SeqLens &lens) {
+  const bool two = dx_src && dx_src != e_src;
+  launch_shift<true>(s, e_src, e_dst, T, N, W, Wfwd, lens, "seq_unalign_dgates", two ? dx_src : nullptr,
+                     two ? dx_dst : nullptr);
+}
+void seq_align_train(hipStream_t s, const float *src, float *dst, int T, int N, int W, int Wfwd,
+                     const SeqLens &lens) {
+  launch_shift<false>(s, src, dst, T, N, W, Wfwd, lens, "seq_align_train");
+}
+void seq_unalign_train(hipStream_t s, const float *src, float *dst, int T, int N, int W, int Wfwd,
+                       const SeqLens &lens) {
+  launch_shift<true>(s, src, dst, T, N, W, Wfwd, lens, "seq_unalign_train");
 }
 
 size_t seq_decodable_scratch_bytes(int T, int N) { return sizeof(int) * ((size_t)T * N + 64); }

@@ -107,6 +107,21 @@ int kctc_nnet_compute_objf(kctcNnet_t n, const float *feats_dev, int T_max, int 
   });
 }
 
+int kctc_nnet_set_length_aware(kctcNnet_t n, int on) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && (on == 0 || on == 1), "kctc_nnet_set_length_aware: on must be 0 or 1");
+    KCTC_REQUIRE(n->trainer.Pending() == 0 && n->evaluator.Pending() == 0,
+                 "kctc_nnet_set_length_aware with minibatches in flight");
+    if (on)
+      for (int c = 0; c < n->nnet.NumComponents(); c++)
+        if (auto *r = dynamic_cast<kctc::nnet2::CuDNNRecurrentComponent *>(&n->nnet.GetComponent(c)))
+          KCTC_REQUIRE(r->Desc().prec == 0,
+                       "kctc_nnet_set_length_aware: bf16 precision is set (it has no length-aware training)");
+    n->trainer.SetLengthAware(on != 0);
+    n->evaluator.SetLengthAware(on != 0);
+  });
+}
+
 int kctc_nnet_enable_dp(kctcNnet_t n, const void *uid128, int rank, int world_size) {
   return kctc_guarded([&] {
     n->activate();
