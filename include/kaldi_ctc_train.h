@@ -211,10 +211,15 @@ int kctc_nnet_set_precision(kctcNnet_t nnet, int precision);
  * components; the other components work row by row, unchanged.  ClipGradient's
  * counters keep counting all T_max * N rows, padding included (a padding
  * row's derivative is zero or dropped by the next RNN below, never clipped
- * into a gradient).  Refused with minibatches in flight and with bf16
- * precision set; kctc_nnet_set_precision(nnet, 1) is refused while it is on;
- * a minibatch of more than 64 utterances fails.  Switching it off restores
- * the default path exactly. */
+ * into a gradient).  So does a front end below the first RNN (FixedAffine,
+ * Affine, RectifiedLinear; see below): it works row by row on padding rows
+ * too, the first RNN's masks drop what it leaves there, and the
+ * RectifiedLinear statistics (value_sum, deriv_sum, count) count all
+ * T_max * N rows, the image of the zero padding rows included.  Refused
+ * with minibatches in flight and with bf16 precision set;
+ * kctc_nnet_set_precision(nnet, 1) is refused while it is on; a minibatch of
+ * more than 64 utterances fails.  Switching it off restores the default path
+ * exactly. */
 int kctc_nnet_set_length_aware(kctcNnet_t nnet, int on);
 
 /* TrainNnetSimple momentum (src/ctc/ctc-nnet-train.cc:194-245, config
@@ -247,6 +252,31 @@ int kctc_nnet_set_momentum(kctcNnet_t nnet, float momentum);
 int kctc_nnet_set_dropout_seed(kctcNnet_t nnet, unsigned long long seed);
 int kctc_nnet_remove_dropout(kctcNnet_t nnet, int *removed);
 int kctc_nnet_set_dropout_scale(kctcNnet_t nnet, float scale);
+
+/* The front end of the recipe's --model-type FT and --add-lda networks
+ * (egs/wsj/s5/steps/ctc/nnet2/make_configs.py:262-280), between the Splice
+ * and the first RNN.  Config lines, in the generator's order:
+ *   FixedAffineComponent matrix=<file>
+ *       (--add-lda; nnet-component.cc:3274-3363) <file> holds one Kaldi
+ *       matrix, text or binary: rows = output dim, cols - 1 = input dim, the
+ *       last column is the bias.  out = in L^T + b.  Not updatable.
+ *   AffineComponent input-dim=<D> output-dim=<hidden_dim> bias-stddev=0
+ *       (FT) the first updatable component; learning rate 0.001 unless given.
+ *   RectifiedLinearComponent dim=<hidden_dim>
+ *       (FT; nnet-component.cc:798-826) out = max(in, 0).  Training adds the
+ *       NonlinearComponent statistics (column sums of the output and of the
+ *       0/1 derivative, and the row count) in fp64 on the device, with no host
+ *       synchronisation; with momentum they go through the delta copy as in
+ *       TrainNnetSimple (stats += delta; delta *= m after every minibatch).
+ *       They are read through kctc_component_nonlinear_stats on a copy of the
+ *       component (kaldi_nnet2_component.h), scaled and added by the averaging
+ *       entry points and kept per rank by the gradient exchange.  A minibatch
+ *       whose updates are skipped (a failed recurrence hand-off: the step
+ *       fails and the parameters stay) is still counted in them, as it is in
+ *       ClipGradient's counters: Backprop had run.
+ *   ClipGradientComponent dim=<hidden_dim> ...
+ * The RNN above does not assume |input| <= 1.  bf16 precision applies to the
+ * RNN components only: the front end stays fp32. */
 
 /* TrainNnetSimple (src/ctc/ctc-nnet-train.cc:185-284) over a background egs
  * reader (include/kaldi_ctc_egs.h, opened with the trainer's minibatch_size /

@@ -108,6 +108,11 @@ int kctc_set_perturb_seed(unsigned long long seed);
 /* ClipGradientComponent: srand() of the handle's own rand() stream that
  * self-repair draws from (a handle starts with srand(0)) */
 int kctc_component_srand(kctcComponent_t c, unsigned seed);
+/* NonlinearComponent statistics of a RectifiedLinearComponent or a
+ * SoftmaxComponent (other types fail): value_sum / deriv_sum (either may be
+ * NULL) get `dim` (= the component's dimension) doubles, zeros for a vector
+ * the component does not hold yet; *count (nullable) the row count. */
+int kctc_component_nonlinear_stats(kctcComponent_t c, double *value_sum, double *deriv_sum, int dim, double *count);
 
 /* Components of a network: a copy of component `index` on the network's
  * device, and the replacement of component `index` by a copy of `c`. */
@@ -116,7 +121,8 @@ int kctc_nnet_set_component(kctcNnet_t nnet, int index, kctcComponent_t c);
 
 /* nnet-am-average's loops over components [0, c_end) (c_end = the last
  * updatable component when skip_last_layer, else all): UpdatableComponent
- * Scale / Add and the SoftmaxComponent statistics' Scale / Add.
+ * Scale / Add and the NonlinearComponent statistics' Scale / Add (Softmax,
+ * RectifiedLinear); a FixedAffineComponent is left alone.
  * kctc_nnet_average_models: nnets[0] = sum_i weights[i] * nnets[i] (weights
  * NULL: 1/num each), nnets[0] scaled first, then the others added in order. */
 int kctc_nnet_scale_params(kctcNnet_t nnet, float scale, int skip_last_layer);

@@ -398,7 +398,7 @@ def _tcheck(st, where):
 def recipe_config(num_rnn=5, input_dim=40, hidden=512, num_targets=41, rnn_mode=2, bidirectional=True,
                   learning_rate=5e-4, max_seq_length=2000, clipping_threshold=30.0, param_stddev=0.02,
                   bias_stddev=0.2, num_layers=1, norm_based_clipping=True, splice_context=(0,),
-                  dropout_proportion=0.0):
+                  dropout_proportion=0.0, model_type="google", hidden_dim=1024, lda_matrix=None, lda_dim=None):
     """Component config lines of the CTC recipe, as written by
     egs/wsj/s5/steps/ctc/nnet2/components.py:73-102 (AddRnnLayer ->
     CuDNNRecurrentComponent + ClipGradientComponent) and an output
@@ -406,12 +406,40 @@ def recipe_config(num_rnn=5, input_dim=40, hidden=512, num_targets=41, rnn_mode=
     offsets containing <= 0 and >= 0 values splice frames).
     dropout_proportion > 0 (train.sh --dropout-proportion) puts the generator's
     "DropoutComponent dim=<out> dropout-proportion=<P>" between every RNN and
-    its ClipGradientComponent (components.py:67-71,94-95)."""
+    its ClipGradientComponent (components.py:67-71,94-95).
+    lda_matrix (a path; train.sh --add-lda true) puts the generator's
+    "FixedAffineComponent matrix=<path>" after the Splice (make_configs.py:
+    262-265); its output dimension is lda_dim, or the spliced dimension when
+    that is None (the generator's lda_dim <= 0) -- the matrix file decides, the
+    argument only sizes the lines after it.  model_type="FT" (train.sh
+    --model-type FT) puts "AffineComponent ... output-dim=<hidden_dim>
+    bias-stddev=0", "RectifiedLinearComponent dim=<hidden_dim>" and a
+    ClipGradientComponent in front of the first RNN (make_configs.py:268-280,
+    components.py:37-55).  The defaults ("google", no LDA) give the text this
+    function gave before these arguments existed."""
     if not 0.0 <= dropout_proportion < 1.0:
         raise ValueError("dropout_proportion must be in [0, 1)")
+    if model_type not in ("google", "FT"):
+        raise ValueError('model_type must be "google" or "FT"')
     ctx = [int(c) for c in splice_context]
     lines = [f"SpliceComponent input-dim={input_dim} context={':'.join(map(str, ctx))}"]
     dim = input_dim * len(ctx)
+    clip = (f"clipping-threshold={clipping_threshold} "
+            f"norm-based-clipping={'true' if norm_based_clipping else 'false'}")
+    if lda_matrix is not None:
+        if any(ch.isspace() for ch in str(lda_matrix)):
+            raise ValueError("lda_matrix: a config line cannot hold a path with white space")
+        lines.append(f"FixedAffineComponent matrix={lda_matrix}")
+        if lda_dim is not None and int(lda_dim) > 0:
+            dim = int(lda_dim)
+    if model_type == "FT":
+        if int(hidden_dim) <= 0:
+            raise ValueError("hidden_dim must be positive")
+        lines.append(f"AffineComponent input-dim={dim} output-dim={int(hidden_dim)} learning-rate={learning_rate} "
+                     f"bias-stddev=0")
+        dim = int(hidden_dim)
+        lines.append(f"RectifiedLinearComponent dim={dim}")
+        lines.append(f"ClipGradientComponent dim={dim} {clip}")
     out = hidden * (2 if bidirectional else 1)
     for _ in range(num_rnn):
         lines.append(f"CuDNNRecurrentComponent input-dim={dim} output-dim={hidden} "
@@ -429,6 +457,26 @@ def recipe_config(num_rnn=5, input_dim=40, hidden=512, num_targets=41, rnn_mode=
 
 _PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 _PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def write_kaldi_matrix(path, m, binary=False):
+    """Write the 2-D array m as one Kaldi float matrix file (Matrix<float>::Write
+    behind the stream header of WriteKaldiObject): what "FixedAffineComponent
+    matrix=<path>" reads, e.g. an lda.mat whose last column is the bias.  Text
+    mode writes 9 significant digits, so either mode gives float32(m) back
+    exactly."""
+    a = np.ascontiguousarray(m, dtype=np.float32)
+    if a.ndim != 2:
+        raise ValueError("write_kaldi_matrix: a 2-D array is needed")
+    with open(path, "wb") as f:
+        if binary:
+            f.write(b"\0BFM " + b"\x04" + np.int32(a.shape[0]).tobytes() + b"\x04" + np.int32(a.shape[1]).tobytes())
+            f.write(a.astype("<f4").tobytes())
+        elif a.shape[1] == 0:
+            f.write(b" [ ]\n")
+        else:
+            rows = ["\n  " + " ".join("%.9g" % float(x) for x in r) + " " for r in a]
+            f.write((" [" + "".join(rows) + "]\n").encode())
 
 
 def philox4x32_10(counter, key):
@@ -1040,6 +1088,18 @@ class Component:
 
     def srand(self, seed):
         _tcheck(lib().kctc_component_srand(self.h, int(seed)), "kctc_component_srand")
+
+    def nonlinear_stats(self):
+        """(value_sum, deriv_sum, count) of a RectifiedLinearComponent or a
+        SoftmaxComponent: the NonlinearComponent statistics as float64 arrays
+        of the component's dimension (zeros for a vector not held yet) and the
+        row count.  Other component types raise."""
+        dim = self.InputDim()
+        v, d = np.zeros(dim, np.float64), np.zeros(dim, np.float64)
+        n = ctypes.c_double()
+        _tcheck(lib().kctc_component_nonlinear_stats(self.h, v.ctypes.data, d.ctypes.data, dim, ctypes.byref(n)),
+                "kctc_component_nonlinear_stats")
+        return v, d, n.value
 
 
 def set_perturb_seed(seed):

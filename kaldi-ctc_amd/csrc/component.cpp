@@ -21,6 +21,8 @@ Component *Component::NewComponentOfType(const std::string &type) {
   if (type == "AffineComponent") return new AffineComponent;
   if (type == "SoftmaxComponent") return new SoftmaxComponent;
   if (type == "DropoutComponent") return new DropoutComponent;
+  if (type == "RectifiedLinearComponent") return new RectifiedLinearComponent;
+  if (type == "FixedAffineComponent") return new FixedAffineComponent;
   return nullptr;
 }
 

@@ -87,7 +87,10 @@ int average_end(const kctc::nnet2::Nnet &n, bool skip_last) {
 }
 
 // the nnet-am-average loops: UpdatableComponent and NonlinearComponent only
-bool averaged(const Component &c) { return c.IsUpdatable() || dynamic_cast<const SoftmaxComponent *>(&c); }
+bool averaged(const Component &c) {
+  return c.IsUpdatable() || dynamic_cast<const SoftmaxComponent *>(&c) ||
+         dynamic_cast<const RectifiedLinearComponent *>(&c);
+}
 
 void nnet_scale(kctcNnetImpl *n, float s, bool skip_last) {
   const int end = average_end(n->nnet, skip_last);
@@ -383,6 +386,32 @@ int kctc_component_srand(kctcComponent_t h, unsigned seed) {
   });
 }
 
+int kctc_component_nonlinear_stats(kctcComponent_t h, double *value_sum, double *deriv_sum, int dim, double *count) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(h, "null argument");
+    h->activate();
+    const std::vector<double> *v = nullptr, *d = nullptr;
+    double n = 0;
+    if (auto *rl = dynamic_cast<RectifiedLinearComponent *>(h->c.get())) {
+      rl->SyncStats();
+      v = &rl->ValueSum(); d = &rl->DerivSum(); n = rl->Count();
+    } else if (auto *sm = dynamic_cast<SoftmaxComponent *>(h->c.get())) {
+      v = &sm->ValueSum(); d = &sm->DerivSum(); n = sm->Count();
+    } else {
+      throw std::invalid_argument(h->c->Type() + " has no NonlinearComponent statistics");
+    }
+    KCTC_REQUIRE(dim == h->c->InputDim(), "kctc_component_nonlinear_stats: dim != the component's dimension");
+    auto put = [&](const std::vector<double> &src, double *dst) {
+      if (!dst) return;
+      std::fill(dst, dst + dim, 0.0);
+      std::copy(src.begin(), src.end(), dst);
+    };
+    put(*v, value_sum);
+    put(*d, deriv_sum);
+    if (count) *count = n;
+  });
+}
+
 int kctc_nnet_get_component(kctcNnet_t n, int index, kctcComponent_t *out) {
   return kctc_guarded([&] {
     KCTC_REQUIRE(n && out, "null argument");
@@ -409,6 +438,7 @@ int kctc_nnet_set_component(kctcNnet_t n, int index, kctcComponent_t h) {
     if (n->nnet.Momentum() != 0.f) {
       if (c->IsUpdatable()) static_cast<UpdatableComponent *>(c)->SetMomentum(n->nnet.Momentum());
       if (auto *cg = dynamic_cast<ClipGradientComponent *>(c)) cg->EnableShadow(true);
+      if (auto *rl = dynamic_cast<RectifiedLinearComponent *>(c)) rl->EnableShadow(true);
     }
     n->nnet.SetComponent(index, c);
     KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));

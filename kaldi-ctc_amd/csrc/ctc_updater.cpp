@@ -396,6 +396,8 @@ void NnetCtcUpdater::Backprop(int T, int N) {  // :320-348
       cg->rng_ = &repair_rng_;  // RepairGradients draws RandUniform() from the process stream
       if (cg->Shadow()) to_update = cg->Shadow();  // momentum: delta_nnet's copy
     }
+    if (auto *rl = dynamic_cast<RectifiedLinearComponent *>(&comp))
+      if (rl->Shadow()) to_update = rl->Shadow();  // ditto: UpdateStats goes to the delta copy
     const CuMatrixBase od(cur->Data(), rows, comp.OutputDim());
     const bool rec = exchange_ && dynamic_cast<CuDNNRecurrentComponent *>(&comp);
     if (rec) exchange_->BeforeRecurrence(S());
@@ -423,6 +425,14 @@ void NnetCtcUpdater::Backprop(int T, int N) {  // :320-348
     ProfScope ps("update");
     static_cast<UpdatableComponent *>(&nnet_->GetComponent(c))->ApplyUpdate(err_word_.p ? static_cast<const unsigned *>(err_word_.p) : nullptr);
   }
+  // momentum: nnet->AddNnet(1.0, *delta_nnet); delta_nnet->Scale(momentum) on the
+  // NonlinearComponent statistics (the parameters' share is ApplyUpdate's).
+  // Not gated by the step's error word: like ClipGradient's counters the
+  // statistics count every minibatch whose Backprop ran, also one whose
+  // parameter updates are skipped.
+  if (nnet_->Momentum() != 0.f)
+    for (int c = first; c < C; c++)
+      if (auto *rl = dynamic_cast<RectifiedLinearComponent *>(&nnet_->GetComponent(c))) rl->FoldShadow(nnet_->Momentum());
 }
 
 }  // namespace nnet2

@@ -9,7 +9,9 @@
 //   Matrix<float>::Write / Read              matrix/kaldi-matrix.cc ("FM" rows cols raw |
 //                                            " [\n  a b \n  c d ]")
 //   InitKaldiOutputStream / InitKaldiInputStream  base/io-funcs.cc ("\0B" binary header)
-// Text floats are written with 9 significant digits (exact round trip).
+// Text numbers are written with Kaldi's 7 significant digits; the writers of
+// vectors, matrices and doubles take `digits` for callers that want an exact
+// text round trip (9 for float, 17 for double; Kaldi reads either).
 #pragma once
 #include <cctype>
 #include <cstdint>
@@ -140,12 +142,12 @@ inline float ReadFloat(std::istream &is, bool binary) {
   if (is.fail()) Fail("ReadBasicType<float>: not a number");
   return (float)v;
 }
-inline void WriteDouble(std::ostream &os, bool binary, double v) {
+inline void WriteDouble(std::ostream &os, bool binary, double v, int digits = 7) {
   if (binary) {
     os.put((char)sizeof(v));
     os.write(reinterpret_cast<const char *>(&v), sizeof(v));
   } else {
-    os << std::setprecision(7) << v << ' ';
+    os << std::setprecision(digits) << v << ' ';
   }
 }
 inline double ReadDouble(std::istream &is, bool binary) {
@@ -216,14 +218,14 @@ inline std::vector<int32_t> ReadIntVector(std::istream &is, bool binary) {
   return v;
 }
 
-inline void WriteFloatVector(std::ostream &os, bool binary, const float *v, long n) {
+inline void WriteFloatVector(std::ostream &os, bool binary, const float *v, long n, int digits = 7) {
   if (binary) {
     WriteToken(os, binary, "FV");
     WriteInt(os, binary, (int32_t)n);
     if (n) os.write(reinterpret_cast<const char *>(v), 4 * (size_t)n);
   } else {
     os << " [ ";
-    for (long i = 0; i < n; i++) os << std::setprecision(7) << v[i] << ' ';
+    for (long i = 0; i < n; i++) os << std::setprecision(digits) << v[i] << ' ';
     os << "]\n";
   }
 }
@@ -255,14 +257,14 @@ inline std::vector<float> ReadFloatVector(std::istream &is, bool binary) {
 }
 
 // Vector<double>::Write / Read ("DV" n raw | " [ a b ]"); a float vector is accepted
-inline void WriteDoubleVector(std::ostream &os, bool binary, const std::vector<double> &v) {
+inline void WriteDoubleVector(std::ostream &os, bool binary, const std::vector<double> &v, int digits = 7) {
   if (binary) {
     WriteToken(os, binary, "DV");
     WriteInt(os, binary, (int32_t)v.size());
     if (!v.empty()) os.write(reinterpret_cast<const char *>(v.data()), 8 * v.size());
   } else {
     os << " [ ";
-    for (double x : v) os << std::setprecision(7) << x << ' ';
+    for (double x : v) os << std::setprecision(digits) << x << ' ';
     os << "]\n";
   }
 }
@@ -293,7 +295,7 @@ inline std::vector<double> ReadDoubleVector(std::istream &is, bool binary) {
   return v;
 }
 
-inline void WriteFloatMatrix(std::ostream &os, bool binary, const float *m, int rows, int cols) {
+inline void WriteFloatMatrix(std::ostream &os, bool binary, const float *m, int rows, int cols, int digits = 7) {
   if (binary) {
     WriteToken(os, binary, "FM");
     WriteInt(os, binary, rows);
@@ -308,7 +310,7 @@ inline void WriteFloatMatrix(std::ostream &os, bool binary, const float *m, int 
   os << " [";
   for (int r = 0; r < rows; r++) {
     os << "\n  ";
-    for (int c = 0; c < cols; c++) os << std::setprecision(7) << m[(size_t)r * cols + c] << ' ';
+    for (int c = 0; c < cols; c++) os << std::setprecision(digits) << m[(size_t)r * cols + c] << ' ';
   }
   os << "]\n";
 }

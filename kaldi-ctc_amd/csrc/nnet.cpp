@@ -110,6 +110,7 @@ void Nnet::SetMomentum(float m) {
   for (auto *c : components_) {
     if (c->IsUpdatable()) static_cast<UpdatableComponent *>(c)->SetMomentum(m);
     if (auto *cg = dynamic_cast<ClipGradientComponent *>(c)) cg->EnableShadow(m != 0.f);
+    if (auto *rl = dynamic_cast<RectifiedLinearComponent *>(c)) rl->EnableShadow(m != 0.f);
   }
 }
 

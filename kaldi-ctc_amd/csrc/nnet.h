@@ -12,6 +12,8 @@
 //   ClipGradientComponent               -> elementwise.hip / clipgrad.hip
 //   AffineComponent                     -> gemm.hip
 //   DropoutComponent                    -> dropout.hip (regenerated Philox mask)
+//   RectifiedLinearComponent            -> nonlinear.hip (device fp64 statistics)
+//   FixedAffineComponent                -> gemm.hip (the LDA transform, not trained)
 //   Nnet                              component list, FirstUpdatableComponent
 //   NnetCtcUpdater                      ComputeForMinibatch: forward, warp-ctc ABI
 //                                       (ctc.hip), accuracy, backprop, SGD.
@@ -127,6 +129,8 @@ struct Rng {  // splitmix64 + Box-Muller (replaces Kaldi's rand()-based RandGaus
   double uniform();  // (0, 1)
   double gauss();
 };
+
+class GradExchange;
 
 // ---- components -------------------------------------------------------------
 class Component {
@@ -491,6 +495,7 @@ class SoftmaxComponent : public Component {
   void Scale(float scale) override;
   void Add(float alpha, const Component &other) override;
   const std::vector<double> &ValueSum() const { return value_sum_; }
+  const std::vector<double> &DerivSum() const { return deriv_sum_; }
   double Count() const { return count_; }
 
  private:
@@ -498,6 +503,93 @@ class SoftmaxComponent : public Component {
   mutable DevBuf ws_;
   std::vector<double> value_sum_, deriv_sum_;
   double count_ = 0;
+};
+
+// RectifiedLinearComponent (nnet-component.h:676; NonlinearComponent base,
+// nnet-component.cc:329-426): the recipe's --model-type FT puts one, between a
+// hidden AffineComponent and a ClipGradientComponent, in front of the first
+// RNN.  The statistics (value_sum, deriv_sum, count) live on the device in
+// fp64 and are added to by Backprop's own pass on the compute stream
+// (nonlinear.h); they come to the host only in Info / Write / Copy / the
+// getters (SyncStats), so a training step gains no host synchronisation.  A
+// vector that is empty in the reference (before the first UpdateStats, or in
+// a file) is all zero on the device and flagged absent; it is written empty.
+class RectifiedLinearComponent : public Component {
+ public:
+  ~RectifiedLinearComponent() override;
+  std::string Type() const override { return "RectifiedLinearComponent"; }
+  int InputDim() const override { return dim_; }
+  int OutputDim() const override { return dim_; }
+  void InitFromString(std::string args, Rng &rng) override;
+  std::string Info() const override;
+  bool BackpropNeedsInput() const override { return false; }
+  void Propagate(const ChunkInfo &, const ChunkInfo &, const CuMatrixBase &in,
+                 CuMatrixBase *out) const override;
+  // in_deriv = out_deriv where out_value > 0; to_update's statistics get
+  // UpdateStats(out_value, the 0/1 derivative), also when in_deriv is null
+  void Backprop(const ChunkInfo &, const ChunkInfo &, const CuMatrixBase &, const CuMatrixBase &out_value,
+                const CuMatrixBase &out_deriv, Component *to_update, CuMatrixBase *in_deriv) const override;
+  void Write(std::ostream &os, bool binary) const override;
+  void Read(std::istream &is, bool binary) override;
+  Component *Copy() const override;
+  void ZeroStats() override;
+  void Scale(float scale) override;
+  void Add(float alpha, const Component &other) override;
+  // host view of the device statistics (synchronises the compute stream)
+  void SyncStats() const;
+  const std::vector<double> &ValueSum() const { return value_sum_; }  // after SyncStats; empty: absent
+  const std::vector<double> &DerivSum() const { return deriv_sum_; }
+  double Count() const { return count_; }
+  // momentum training (ctc-nnet-train.cc:194-245): delta_nnet's copy starts
+  // with zero statistics (Nnet::SetZero scales them by 0), every Backprop's
+  // UpdateStats goes to it, and after the minibatch FoldShadow does
+  // AddNnet(1.0, delta) and delta->Scale(momentum) on the statistics
+  void EnableShadow(bool on);
+  RectifiedLinearComponent *Shadow() const { return shadow_; }
+  void FoldShadow(float momentum);
+  // nnet-am-average over data-parallel ranks: the statistics summed over the
+  // ranks, on stream s.  The exchange sums floats: the sums travel as their
+  // fp32 image (counts stay exact below 2^24)
+  void AllReduceStats(GradExchange &ex, hipStream_t s);
+
+ private:
+  void SetDim(int dim);  // allocates and zeroes the device statistics
+  double *Dev() const { return static_cast<double *>(dev_.p); }
+  long NumStats() const { return 2L * dim_ + 1; }
+  int dim_ = 0;
+  DevBuf dev_;  // fp64: value_sum[dim], deriv_sum[dim], count
+  bool have_value_ = false, have_deriv_ = false;
+  mutable std::vector<double> value_sum_, deriv_sum_;
+  mutable double count_ = 0;
+  mutable DevBuf ws_;
+  RectifiedLinearComponent *shadow_ = nullptr;
+};
+
+// FixedAffineComponent (nnet-component.cc:3274-3363; the recipe's --add-lda
+// puts "FixedAffineComponent matrix=<dir>/lda.mat" after the spliced input):
+// out = in L^T + b with L, b the matrix file's columns [0, cols-1) and cols-1.
+// Not updatable, no statistics.
+class FixedAffineComponent : public Component {
+ public:
+  std::string Type() const override { return "FixedAffineComponent"; }
+  int InputDim() const override { return in_dim_; }
+  int OutputDim() const override { return out_dim_; }
+  void InitFromString(std::string args, Rng &rng) override;
+  std::string Info() const override;
+  bool BackpropNeedsInput() const override { return false; }
+  bool BackpropNeedsOutput() const override { return false; }
+  void Propagate(const ChunkInfo &, const ChunkInfo &, const CuMatrixBase &in,
+                 CuMatrixBase *out) const override;
+  void Backprop(const ChunkInfo &, const ChunkInfo &, const CuMatrixBase &, const CuMatrixBase &,
+                const CuMatrixBase &out_deriv, Component *, CuMatrixBase *in_deriv) const override;
+  void Write(std::ostream &os, bool binary) const override;
+  void Read(std::istream &is, bool binary) override;
+  Component *Copy() const override;
+
+ private:
+  void Init(const std::vector<float> &linear, const std::vector<float> &bias, int rows, int cols);
+  int in_dim_ = 0, out_dim_ = 0;
+  DevBuf params_;  // [out][in] followed by [out], AffineComponent's layout
 };
 
 class AffineComponent : public UpdatableComponent {

@@ -194,6 +194,15 @@ int kctc_nnet_average_params(kctcNnet_t n) {
     n->activate();
     const int world = n->dp->WorldSize();
     for (int c = 0; c < n->nnet.NumComponents(); c++) {
+      // the tool's NonlinearComponent share: RectifiedLinear's statistics
+      // (a sum over one rank is the identity, and exact)
+      if (auto *rl = dynamic_cast<kctc::nnet2::RectifiedLinearComponent *>(&n->nnet.GetComponent(c))) {
+        if (world > 1) {
+          rl->Scale(1.f / (float)world);
+          rl->AllReduceStats(*n->dp, n->stream);
+        }
+        continue;
+      }
       auto *u = dynamic_cast<kctc::nnet2::UpdatableComponent *>(&n->nnet.GetComponent(c));
       if (!u) continue;
       if (world > 1) u->Scale(1.f / (float)world);
