@@ -68,6 +68,10 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   // bf16 (configs[4], every wave an element wave) measured faster with the
   // whole pointwise backward in the cell (3.65 vs 3.46 us/step)
   constexpr bool PRE = !BF;
+  // stacked: the operands come through LDS from waves 6 and 7 (IOA, io_fetch
+  // below), the dGates rows leave through the estg stage with or without a
+  // streaming consumer (RST), and wave 4 stores the aggregated epoch (GF4)
+  constexpr bool IOA = STK, RST = STK, GF4 = STK;
   using AT = typename std::conditional<BF, __bf16, _Float16>::type;
   using AV = typename std::conditional<BF, bf16x8, halfx8>::type;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -169,7 +173,14 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   // from the has_r threads, as zeros
   const bool has_r = tid < 16 * U;
   const bool has_e = tid < (STK ? 8 : 16) * U;
-  const int en = tid / U, eu = tid - en * U;
+  // IOA (stacked): the last 8 U threads, waves 6 and 7, are the element
+  // threads' twins -- thread tid of them fetches the operands of element
+  // tid - (NTH - 8 U) into the LDS stage (io_fetch below) and does nothing
+  // else of an element's work
+  const bool io_lane = IOA && tid >= NTH - 8 * U;
+  const bool io_wave = IOA && __builtin_amdgcn_readfirstlane(tid >> 6) >= NWV - 8 * U / 64;
+  const int etid = io_lane ? tid - (NTH - 8 * U) : tid;
+  const int en = etid / U, eu = etid - en * U;
   const int n = n0 + en;
   const bool live = has_e && n < nend;
   float carry = 0.f, bsx[NW], bsh[NW], dxk[NW], eg[NW], cg[NW], ng[NW], cmx[NW], cme[NW];
@@ -226,7 +237,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
         if (MODE == kGru) cme[q] = fmaxf(cme[q], fabsf(eg[q]));
       }
     }
-    if (p.e_sc1 || (BF && p.dxt != nullptr)) {
+    if (RST || p.e_sc1 || (BF && p.dxt != nullptr)) {
 #pragma unroll
       for (int q = 0; q < NW; q++) estg[en * NW * U + q * U + eu] = MODE == kGru ? dxk[q] : eg[q];
       if (MODE == kGru && BF && p.dxt != nullptr) {
@@ -249,8 +260,11 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   typedef float __attribute__((address_space(1))) *gfp;
   const int t_first = d == 0 ? T - 1 : 0;
   const long ystep = (d == 0 ? -1 : 1) * (long)N * ldy, gstep = (d == 0 ? -1 : 1) * (long)N * ldg;
-  const long yel = ((long)t_first * N + n) * ldy + (long)d * H + u0 + eu;
-  const long gel = ((long)t_first * N + n) * ldg + (long)d * NW * H + u0 + eu;
+  // (a fetching twin of a dead row reads a live row's operands: every lane of
+  // the IO waves issues every load, so that their vmcnt counts are exact)
+  const int nld = io_lane ? max(n0, min(n, nend - 1)) : n;
+  const long yel = ((long)t_first * N + nld) * ldy + (long)d * H + u0 + eu;
+  const long gel = ((long)t_first * N + nld) * ldg + (long)d * NW * H + u0 + eu;
   const float *dy_e = p.dy + yel;
   const float *g_e = p.G + gel;
   const float *aux_e = p.aux + yel;
@@ -278,12 +292,12 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
     }
     dy_p += ystep; g_p += gstep; aux_p += ystep; prv_p += ystep;
   };
-  // STK: the operands run two steps ahead.  Step ks loads those of step
-  // ks + 2 into n* behind its hand-off wait; directly before, behind that same
-  // wait (in-order vmcnt: it retired the loads of step ks - 1 too), n* -- the
-  // operands of step ks + 1 -- rotate into c*, where coef() of step ks + 1
-  // finds them a whole step old.  The cell of step ks runs after that rotate:
-  // its dy waits one stage longer, in xdy.
+  // n* -> c*, where coef() and the cell read.  (STK: in front of the loop
+  // only, for step 0; from step 1 on the element waves read c* from the LDS
+  // slot the IO waves filled and issue no global load in the step loop)
+  // (xdy, the stage dy had when the operands ran two steps ahead, has no
+  // reader left; without the copy the compiler orders some instructions of the
+  // plain split-fp16 kernels differently, and those stay the parent's to the letter)
   float xdy = 0.f;
   auto rotate = [&]() {
     xdy = cdy;
@@ -298,6 +312,40 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
       for (int q = 0; q < NW; q++) asm volatile("" : "+v"(cg[q]));
     }
   };
+  // IOA: the operand stage, a ring of three slots [NOP][8 U] floats behind
+  // estg -- slot j % 3 holds the operands of step j (dy, the NW gates, c / the
+  // GRU's aux, the previous state), element e at [op][e].  An IO wave fills
+  // its 64 elements of an operand with one LDS-DMA (no register, no LDS write
+  // instruction; inline asm, invisible to the compiler's wait counts, see
+  // dma_lds_dword).  The pointers stay on the last step once there (io_j):
+  // the fetches past the end load it again into a slot nobody reads, so that
+  // the wave's queue has the same shape at every step.
+  constexpr int NOP = NW + 3, OSL = NOP * 8 * U;  // operands; floats per slot
+  float *ostg = estg + 16 * NW * U;
+  static_assert(!IOA || (2 * 16 * AP * 2 + (NTH * 4 > 2 * 16 * U * NW ? NTH * 4 : 2 * 16 * U * NW) * 4 + 16 * NW * U * 4 +
+                         3 * OSL * 4 <= 96 * 1024), "the operand stage fits the launch's LDS (bwd6_lds_bytes: >= 96 KB)");
+  int io_j = 0;  // the step the IO lanes' pointers stand on
+  auto io_fetch = [&](int slot) {
+    const unsigned dst = __builtin_amdgcn_readfirstlane(
+        (unsigned)reinterpret_cast<uintptr_t>(ostg + slot * OSL + (w - (NWV - 8 * U / 64)) * 64));
+    dma_lds_dword((const float *)dy_p, dst);
+#pragma unroll
+    for (int q = 0; q < NW; q++) dma_lds_dword((const float *)(g_p + q * H), dst + (1 + q) * 8 * U * 4);
+    dma_lds_dword((const float *)aux_p, dst + (1 + NW) * 8 * U * 4);
+    // (the first frame's previous state: a valid address, the value dropped by coef())
+    dma_lds_dword((const float *)(io_j < T - 1 ? prv_p : aux_p), dst + (2 + NW) * 8 * U * 4);
+    if (io_j < T - 1) {
+      dy_p += ystep; g_p += gstep; aux_p += ystep; prv_p += ystep;
+      io_j++;
+    }
+  };
+  // what an IO wave leaves in flight in front of a step's first barrier: the
+  // fetch and the 4 partial-dh stores of the step before (see the loop)
+  auto io_wait = [&]() {
+    if constexpr (NOP == 7) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+  };
+  static_assert(!IOA || CTW == 4, "an IO wave's 4 partial-dh stores a step");
   // bf16 packed operands (p.dxt): the step's DX tile is staged in estg and the
   // GRU's E tile in estg2 during the cell phase; the next step writes them as
   // 16-B bf16 chunks (DX rows; DX^T and E^T columns of 8 frames)
@@ -353,7 +401,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
       return;
     }
     if (!live) return;
-    if (p.e_sc1) {  // DX (== E for LSTM) went out through estg already
+    if (RST || p.e_sc1) {  // DX (== E for LSTM) went out through estg already
       if (MODE == kGru) {
 #pragma unroll
         for (int q = 0; q < NW; q++) ep[q * H] = eg[q];
@@ -392,12 +440,20 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
   const int ereg = STK ? (eu & 3) : (en & 3);
   prefetch(T - 1);
   rotate();
-  if constexpr (STK) {
-    if (T > 1) prefetch(T - 2);
-    // landed before the loop: step 0 has no hand-off wait to rotate behind
-    asm volatile("" : "+v"(ndy), "+v"(na), "+v"(nap));
-#pragma unroll
-    for (int q = 0; q < NW; q++) asm volatile("" : "+v"(ng[q]));
+  if constexpr (IOA) {
+    // step 0's operands came directly (above); those of steps 1 and 2 are in
+    // their slots before the loop (the first read of a slot follows step 0's
+    // two barriers), so that every wait in the loop finds the same queue
+    if (io_wave) {
+      if (T > 1) {
+        io_j = 1;  // (prefetch() moved the pointers on)
+      } else {
+        dy_p -= ystep; g_p -= gstep; aux_p -= ystep; prv_p -= ystep;
+      }
+      io_fetch(1);
+      io_fetch(2);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
   }
   if constexpr (PRE) {
     if (!STK || has_e) coef(T - 1, true);
@@ -453,16 +509,26 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
     // self-tagged (issued after the first barrier): the LAST 16 CPR threads,
     // i.e. the waves past the element waves when there are any, store while
     // the element waves do the cell
-    const int et = dtag ? tid - (NTH - 16 * CPR) : tid;
+    // (IOA: from wave 4 on -- the 8 live rows' chunks stay on waves 4 and 5
+    // for the GRU's 12 chunks a row too, off the IO waves)
+    const int et = dtag ? tid - (IOA ? NTH / 2 : NTH - 16 * CPR) : tid;
     const int rn = et >= 0 ? et / CPR : 16, c = et - rn * CPR;
     if (rn < 16 && n0 + rn < nend) {
       const int q = (c * 4) / U, u = (c * 4) % U;
       const u32x4 v = *reinterpret_cast<const u32x4 *>(estg + rn * NW * U + c * 4);
       const int off = (int)(((long)(n0 + rn) * ldg + (long)d * NW * H + q * H + u0 + u) * 4);
+      if constexpr (RST) {
+        // (no streaming consumer: the same chunks with the plain policy)
+        if (!p.e_sc1) {
+          __builtin_amdgcn_raw_buffer_store_b128(v, rsrc(p.DX + (long)tt * N * ldg, (unsigned)(N * ldg * 4)), off, 0, 0);
+          return;
+        }
+      }
       __builtin_amdgcn_raw_buffer_store_b128(v, rsrc(p.DX + (long)tt * N * ldg, (unsigned)(N * ldg * 4)), off, 0, 16);
     }
   };
   int t_prev = -1;
+  int sl3 = 0;  // IOA: ks % 3, the operand slot of this step
   for (int k = T - 1; k >= 0 && !bad; k--) {
     const int t = d == 0 ? k : T - 1 - k;
     const int ks = T - 1 - k;  // steps done before this one
@@ -510,7 +576,16 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
         // the write-through dGates rows behind the aggregated epoch): the
         // wait itself, in front of the step's first barrier, where this wave
         // idles for the loading waves anyway
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // IOA, waves 6 and 7: the exact wait.  Such a wave's queue, oldest
+        // first, is F(ks - 2), S(ks - 2), F(ks - 1), S(ks - 1) -- F(j) the
+        // NOP loads of the fetch it issued behind the first barrier of step j
+        // (the operands of step j + 3), S(j) its 4 partial-dh stores of step
+        // j -- and it needs F(ks - 2) landed (step ks + 1 reads that slot
+        // behind this step's barriers) and S(ks - 2) retired (the ring of two
+        // images): NOP + 4 stay in flight.  (The trace's stamps are stores of
+        // these waves too: a traced run drains.)
+        if (io_wave && !p.trace) io_wait();
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       } else {
         u32x4 v[PER];
         // unconditional loads (a dead row quad at an offset past the buffer:
@@ -521,6 +596,18 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
         for (int i = 0; i < PER; i++) v[i] = ld_sc1(rs, hoff(i));
         if constexpr (PRE) {
           __builtin_amdgcn_sched_barrier(0);
+          if constexpr (IOA) {
+            // this step's operands, from the slot the IO waves filled (landed
+            // before the last step's first barrier)
+            if (has_e) {
+              const float *os = ostg + sl3 * OSL + tid;
+              cdy = os[0];
+#pragma unroll
+              for (int q = 0; q < NW; q++) cg[q] = os[(1 + q) * 8 * U];
+              ca = os[(1 + NW) * 8 * U];
+              cap_ld = os[(2 + NW) * 8 * U];
+            }
+          }
           if (!STK || has_e) coef(k);  // while the hand-off loads are in flight
           // (pinned here: IR passes had sunk the coefficients past the loads' wait)
 #pragma unroll
@@ -557,17 +644,10 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
         sm = __builtin_bit_cast(floatx4, v[0]);
 #pragma unroll
         for (int i = 1; i < PER; i++) sm += __builtin_bit_cast(floatx4, v[i]);
-        // (HO4: the element waves are loading waves, and the rotate stays on
-        // their arm, in front of the join with the waves that did not load)
-        if constexpr (HO4) rotate();
       }
       if (ho_wave) st4(red + (long)(pg * POS + pos) * 4, sm);
       REC_TRACE(ks, 2);
       REC_TRACE_W(ks, 24);
-      // behind the hand-off wait, which retired the last step's prefetch too
-      // (on this path: a rotate behind the branches' join waits again, for
-      // the loads the compiler must assume on the path without a hand-off)
-      if constexpr (STK && !HO4) rotate();
       // behind this step's hand-off loads: the write-through copies for the
       // streamed dx GEMM -- the previous step's dGates rows (staged in LDS)
       // and the epoch the last signal drained (step ks - 2's rows).  Issued
@@ -575,16 +655,12 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
       // poll, which waits for every older store (one vmcnt for loads and stores)
       // (self-tagged: after the barrier below, which orders it behind the
       // previous step's book() writes of estg -- no signal barrier in between)
-      if (p.e_sc1 && !dtag) e_sc1_store(t_prev);
-    } else {
-      if constexpr (STK) rotate();  // step 0: nothing outstanding (see the prologue)
+      if ((RST || p.e_sc1) && !dtag) e_sc1_store(t_prev);
     }
     asm volatile("" ::: "memory");
     // behind the hand-off loads: next step's operands, last step's row-major dGates
     if (t_prev >= 0 && !(!PRE && bfp && ks > 0)) e_store(t_prev);
-    if constexpr (STK) {
-      if (k > 1) prefetch(k - 2);
-    } else {
+    if constexpr (!IOA) {  // (IOA: the IO waves fetch, behind the barrier)
       if (k > 0) prefetch(k - 1);
     }
     __syncthreads();
@@ -603,9 +679,14 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
     // -> epoch ks (rows of step k out at epoch k + 3; no wait at the end of
     // a step is part of this);
     // flagged: its signal of step ks - 1 drained the rows of step ks - 2
-    if (gflag && ks > 0 && tid == 0)
+    if (gflag && ks > 0 && tid == (GF4 ? NTH / 2 : 0))
       __hip_atomic_store(gflag, (unsigned)(dtag ? ks : ks + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (dtag && p.e_sc1 && ks > 0) e_sc1_store(t_prev);
+    if (dtag && (RST || p.e_sc1) && ks > 0) e_sc1_store(t_prev);
+    if constexpr (IOA) {
+      // the operands of step ks + 3 into the slot step ks read in front of
+      // this barrier: two step periods until the wait above needs them
+      if (io_wave) io_fetch(sl3);
+    }
     if (has_e) {
       float dhr = 0.f;
       if (ks > 0) {
@@ -618,7 +699,7 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
 #pragma unroll
         for (int gg = 0; gg < NGRP; gg++) dhr += rr[gg];
       }
-      float dh = (STK ? xdy : cdy) + dhr;
+      float dh = cdy + dhr;
       if constexpr (PRE) {
         if (MODE == kLstm) {
           const float dc = dh * kc[0] + carry;
@@ -883,12 +964,16 @@ __global__ __launch_bounds__(NTH, 1) void rnn_bwd_rec6(RecParams p) {
     REC_TRACE(ks, 4);
     if constexpr (!STK) rotate();
     t_prev = t;
+    sl3 = sl3 == 2 ? 0 : sl3 + 1;
     REC_TRACE(ks, 5);
+  }
+  if constexpr (IOA) {
+    if (io_wave) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the fetches past the last step land
   }
   if (dtag) __syncthreads();  // the last step's book() writes of estg, before e_sc1_store reads them
   if (t_prev >= 0 && !bad) e_store(t_prev);
   if (!bad) {
-    if (p.e_sc1 && t_prev >= 0) e_sc1_store(t_prev);
+    if ((RST || p.e_sc1) && t_prev >= 0) e_sc1_store(t_prev);
     signal_epoch(myflag, (unsigned)(T + 2), 0);  // the last step's rows are out
     if (gflag) {  // every producer's last rows are out
       wait_flags6(flag6(p, grp, d, 0, NWG), NWG, (unsigned)(T + 2), p.err, bad, &bad_lds, p.poll_sleep);

@@ -74,6 +74,10 @@ const void *rnn_rec6_select(const RnnDesc &d, int N, bool fwd, int cfg[5]);
 // workgroup, dynamic LDS bytes, XCDs a pinned v6 launch occupies (bit mask),
 // workgroups per (row group, direction), RecParams::xpd}; nothing is launched
 void rnn_rec_plan(const RnnDesc &d, int N, bool fwd, long plan[8]);
+// test hook (test_hooks.h kctc_test_rnn_colmax_offset): byte offset, in the
+// workspace of (d, T, N), of the dGates column maxima a v6 backward
+// recurrence leaves ([2][dirs][nw H] float bits: DX, then the GRU's E)
+size_t rnn_ws_colmax_offset(const RnnDesc &d, int T, int N);
 
 // Residency gate of the gradient exchange.  Every workgroup
 // of a v6 backward recurrence adds 1 to a per-device 64-bit registration

@@ -371,5 +371,9 @@ void rnn_rec_plan(const RnnDesc &d, int N, bool fwd, long plan[8]) {
   plan[0] = p.ver, plan[1] = p.U, plan[2] = p.grid, plan[3] = p.nth, plan[4] = (long)p.lds, plan[5] = p.xcds,
   plan[6] = p.nwg, plan[7] = p.xpd;
 }
+size_t rnn_ws_colmax_offset(const RnnDesc &d, int T, int N) {
+  const RnnWs ws(d, T, N, nullptr);
+  return ws.pack_off + ws.lay.cme;
+}
 
 }  // namespace kctc

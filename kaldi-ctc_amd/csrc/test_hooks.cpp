@@ -177,4 +177,15 @@ int kctc_test_rec_plan(int mode, int prec, int H, int dirs, int N, int fwd, long
   }
 }
 
+long kctc_test_rnn_colmax_offset(int mode, int prec, int D, int H, int dirs, int T, int N) {
+  try {
+    kctc::RnnDesc d;
+    d.mode = mode; d.D = D; d.H = H; d.dirs = dirs;
+    kctc::rnn_set_precision(d, prec);
+    return (long)kctc::rnn_ws_colmax_offset(d, T, N);
+  } catch (...) {
+    return -1;
+  }
+}
+
 }  // extern "C"

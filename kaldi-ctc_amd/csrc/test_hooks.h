@@ -82,6 +82,11 @@ int kctc_test_rec6_select(int mode, int prec, int H, int dirs, int N, int fwd, i
  * (generic: XCD slots per direction, 0 in plain block mapping; v6: 1 when
  * pinned)}.  Nothing is launched. */
 int kctc_test_rec_plan(int mode, int prec, int H, int dirs, int N, int fwd, long plan[8]);
+/* Byte offset, in the workspace of a one-layer RNN (mode, prec, D, H, dirs) at
+ * (T, N), of the dGates column maxima its v6 backward recurrence leaves:
+ * [2][dirs][nw H] floats as bits (DX, then the GRU's E; max over all frames of
+ * |value|).  -1 on error.  Nothing is launched. */
+long kctc_test_rnn_colmax_offset(int mode, int prec, int D, int H, int dirs, int T, int N);
 #ifdef __cplusplus
 }
 #endif
