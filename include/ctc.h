@@ -99,6 +99,46 @@ int mictc_set_frame_group(int m);
  * queries. */
 int mictc_set_win(int on);
 
+/* ---- CTC forced alignment (Viterbi; csrc/ctc_align.hip) -------------------
+ * The best path of each utterance through its own transcript: with
+ * lp[t][a] the log-softmax of frame t and l' the blank-interleaved labels
+ * (S = 2L+1 states, even ones blank),
+ *   v_0(0) = lp[0][blank], v_0(1) = lp[0][l'_1], the rest -inf;
+ *   v_t(s) = lp[t][l'_s] + max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2)),
+ * the last candidate only for odd s >= 2 with l'_s != l'_{s-2}.  A later
+ * candidate wins only if it is strictly greater (staying beats a step of one
+ * beats a skip); the path ends in state S-1 unless state S-2 scores strictly
+ * higher.
+ *  - activations [maxT][minibatch][alphabet_size] float, DEVICE, un-normalised,
+ *    maxT = max(input_lengths); rows t >= input_lengths[n] are never read
+ *    (they may hold NaN).
+ *  - flat_labels, label_lengths, input_lengths: HOST, consumed before return.
+ *  - ali_dev int [maxT][minibatch], DEVICE: row t*minibatch+n is the symbol
+ *    (blank included) of frame t of utterance n, -1 for t >= input_lengths[n].
+ *  - scores_dev double [minibatch], DEVICE: log-probability of that path.
+ *  - An utterance with T == 0 or L + repeats > T gets all -1 and score -inf;
+ *    L == 0 gives the all-blank path.
+ *  - workspace: DEVICE, >= mictc_get_align_workspace_size() bytes (it holds
+ *    the normalised log-probs and 2 bits of back-pointer per frame and state).
+ * Stream-ordered: never synchronises, allocates no device memory.  Invalid
+ * lengths, L > 639, a label out of range or equal to blank_label and null
+ * pointers return CTC_STATUS_INVALID_VALUE and enqueue nothing.
+ * Deterministic (no atomics). */
+ctcStatus_t mictc_get_align_workspace_size(const int *label_lengths, const int *input_lengths,
+                                           int alphabet_size, int minibatch, size_t *size_bytes);
+ctcStatus_t mictc_ctc_align_async(const float *activations, const int *flat_labels,
+                                  const int *label_lengths, const int *input_lengths,
+                                  int alphabet_size, int minibatch, int *ali_dev, double *scores_dev,
+                                  void *workspace, ctcStream_t stream, int blank_label);
+
+/* TEST KNOB: 1 (default) runs the Viterbi recursion with one state per thread
+ * wherever 512 threads hold the longest label sequence (S <= 512) and with 512
+ * threads of 3 states beyond; 0 runs the 3-state kernel for every batch, so
+ * that the tests reach it at small sizes.  Process-global like mictc_set_win;
+ * same results either way (tests/test_ctc_align_gpu.py).  Returns the
+ * previous value; on < 0 only queries. */
+int mictc_set_align_kernel(int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,10 @@
  *                               vector-sum (steps/ctc/train.sh:469-510)
  *   kctc_am_nnet_adjust_priors <- nnet-adjust-priors
  *   kctc_nnet_insert         <- nnet-insert (src/nnet2/nnet-functions.cc:39-55)
+ *   kctc_nnet_align / kctc_nnet_align_egs
+ *                            <- CTC forced alignment of a batch / an egs archive
+ *                               (an extension; writes the Int32Vector table that
+ *                               nnet-ctc-relabel-egs reads)
  * Return 0 on success (kctc_last_error() describes a failure).
  */
 #ifndef KALDI_CTC_AMD_KALDI_CTC_DECODE_H_
@@ -138,6 +142,35 @@ int kctc_nnet_insert(kctcNnet_t nnet, int insert_at, const char *config, unsigne
  * tot_like / tot_weight), total accuracy, total weight (sum of labels). */
 int kctc_nnet_compute_prob(kctcNnet_t nnet, const char *rspecifier, long *num_examples, double *tot_like,
                            double *tot_accuracy, double *tot_weight);
+
+/* ---- CTC forced alignment (an extension; the kernels: ctc.h) -------------------
+ * kctc_nnet_align: on which frames does the model place each label of a given
+ * transcript.  feats_dev, T_max, N, num_frames as for kctc_nnet_propagate_seq
+ * (N <= 64): the variable-length forward, so every utterance is aligned as if
+ * it were run alone, then mictc_ctc_align_async on the network's stream with
+ * blank 0 and input lengths num_frames (the updater's rule: NumFrames minus
+ * the ignored context frames, none here).  The alignment runs on un-normalised
+ * activations: of a network that ends in a SoftmaxComponent, on that
+ * component's input (same result as without the Softmax).  flat_labels,
+ * label_lengths: host, symbol ids (label = pdf + 1).  ali_host: T_max*N ints,
+ * row t*N+n the symbol of frame t of utterance n (blank 0 included), -1 for
+ * t >= num_frames[n] and for every frame of an utterance whose labels do not
+ * fit (L + repeats > T); scores_host: N doubles, the log-probability of each
+ * path (-inf: does not fit). */
+int kctc_nnet_align(kctcNnet_t nnet, const float *feats_dev, int T_max, int N, const int *num_frames,
+                    const int *flat_labels, const int *label_lengths, int *ali_host, double *scores_host);
+
+/* Aligns every example of an egs archive (binary "ark:", read as
+ * kctc_nnet_sum_posteriors reads it: batches of minibatch_size (1..64) in
+ * archive order, each example from its own start offset) to its own labels
+ * and writes, per example key, the alignment as a Kaldi Int32Vector to a
+ * binary "ark:" -- the table nnet-ctc-relabel-egs and ali-to-post read.
+ * Symbol ids as they are (blank 0, label = pdf + 1).  Examples whose labels do
+ * not fit are counted and not written.  Outputs (nullable): examples written,
+ * examples that do not fit, the sum of the written paths' log-probabilities
+ * and of their frames. */
+int kctc_nnet_align_egs(kctcNnet_t nnet, const char *egs_rspecifier, const char *ali_wspecifier,
+                        int minibatch_size, long *num_done, long *num_infeasible, double *tot_score, long *tot_frames);
 
 #ifdef __cplusplus
 }

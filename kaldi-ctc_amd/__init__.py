@@ -174,6 +174,77 @@ def compute_ctc_loss(acts, flat_labels, label_lengths, input_lengths, want_grad=
     return costs, grads
 
 
+def ctc_align_kernel(on=-1):
+    """One-state-per-thread Viterbi kernel for short label sequences on (1,
+    default) / off (0: the 512-thread, 3-state kernel for every batch)
+    (mictc_set_align_kernel); returns the previous value (on < 0: query only)."""
+    return lib().mictc_set_align_kernel(int(on))
+
+
+def ctc_align_workspace_size(label_lengths, input_lengths, alphabet_size):
+    ll = np.ascontiguousarray(label_lengths, dtype=np.int32)
+    il = np.ascontiguousarray(input_lengths, dtype=np.int32)
+    out = ctypes.c_size_t()
+    st = lib().mictc_get_align_workspace_size(ll.ctypes.data, il.ctypes.data, int(alphabet_size), len(ll),
+                                              ctypes.byref(out))
+    if st != 0:
+        raise CtcError(st, "mictc_get_align_workspace_size")
+    return out.value
+
+
+def ctc_align(acts, flat_labels, label_lengths, input_lengths, blank=0, stream=None, workspace=None):
+    """CTC forced alignment (mictc_ctc_align_async) of a torch CUDA tensor acts
+    [T, N, A] (float32, un-normalised) to the given transcripts.  Returns
+    (ali int32 CUDA tensor [T, N]: the symbol of every frame, blank included,
+    -1 on the padding rows and for an utterance whose labels do not fit;
+    scores np.float64 [N]: the log-probability of each path, -inf likewise)."""
+    import torch
+    assert acts.is_cuda and acts.dtype == torch.float32 and acts.is_contiguous()
+    T, N, A = acts.shape
+    fl = np.ascontiguousarray(flat_labels, dtype=np.int32)
+    if fl.size == 0:
+        fl = np.zeros(1, np.int32)
+    ll = np.ascontiguousarray(label_lengths, dtype=np.int32)
+    il = np.ascontiguousarray(input_lengths, dtype=np.int32)
+    if len(il) != N or len(ll) != N or (N and int(il.max()) > T):
+        raise CtcError(2, "ctc_align")
+    if workspace is None:
+        workspace = torch.empty(ctc_align_workspace_size(ll, il, A), dtype=torch.uint8, device=acts.device)
+    # the call fills the rows below max(input_lengths); T may be longer
+    ali = torch.full((T, N), -1, dtype=torch.int32, device=acts.device)
+    scores = torch.empty(N, dtype=torch.float64, device=acts.device)
+    s = _stream_handle(stream)
+    if stream is not None:
+        torch.cuda.current_stream().synchronize()  # ali's fill ran on the current stream
+    st = lib().mictc_ctc_align_async(acts.data_ptr(), fl.ctypes.data, ll.ctypes.data, il.ctypes.data, A, N,
+                                     ali.data_ptr(), scores.data_ptr(), workspace.data_ptr(), s, blank)
+    if st != 0:
+        raise CtcError(st, "mictc_ctc_align_async")
+    if stream is not None:
+        torch.cuda.synchronize()  # the scores' copy below runs on the current stream
+    return ali, scores.cpu().numpy()
+
+
+def read_int_vector_ark(path):
+    """Binary Kaldi archive of Int32Vector (what Nnet.align_egs writes and
+    ali-to-post reads) -> dict key -> np.int32 array, in archive order."""
+    if str(path).startswith("ark:"):
+        path = str(path)[4:]
+    out = {}
+    with open(path, "rb") as f:
+        data = f.read()
+    p = 0
+    while p < len(data):
+        sp = data.index(b" ", p)
+        key = data[p:sp].decode()
+        if data[sp + 1:sp + 3] != b"\0B" or data[sp + 3] != 4:
+            raise KctcError(f"{path}: entry {key!r} is not a binary Int32Vector")
+        n = int(np.frombuffer(data, np.int32, 1, sp + 4)[0])
+        out[key] = np.frombuffer(data, np.int32, n, sp + 8).copy()
+        p = sp + 8 + 4 * n
+    return out
+
+
 class RnnError(RuntimeError):
     pass
 
@@ -806,6 +877,36 @@ class Nnet:
         _tcheck(lib().kctc_nnet_sum_posteriors(self.h, str(rspecifier).encode(), minibatch_size, s.ctypes.data, A,
                                                ctypes.byref(fr), ctypes.byref(ne)), "sum_posteriors")
         return s, fr.value, ne.value
+
+    def align(self, feats, T, N, num_frames, flat_labels, label_lengths):
+        """CTC forced alignment of a variable-length batch (kctc_nnet_align;
+        feats as for train_step, N <= 64, every utterance as if run alone) ->
+        (ali np.int32 [T, N]: the symbol of every frame, blank 0 included, -1
+        for t >= num_frames[n] and for an utterance whose labels do not fit;
+        scores np.float64 [N]: the log-probability of each path)."""
+        self._check_feats(feats, T, N)
+        nf = np.ascontiguousarray(num_frames, dtype=np.int32)
+        fl = np.ascontiguousarray(flat_labels, dtype=np.int32)
+        if fl.size == 0:
+            fl = np.zeros(1, np.int32)
+        ll = np.ascontiguousarray(label_lengths, dtype=np.int32)
+        if len(nf) != N or len(ll) != N or fl.size < int(ll.sum()):
+            raise KctcError("align: num_frames / label_lengths must have N entries and flat_labels their sum")
+        ali = np.empty((T, N), np.int32)
+        scores = np.empty(N, np.float64)
+        _tcheck(lib().kctc_nnet_align(self.h, _ptr(feats), T, N, nf.ctypes.data, fl.ctypes.data, ll.ctypes.data,
+                                      ali.ctypes.data, scores.ctypes.data), "nnet_align")
+        return ali, scores
+
+    def align_egs(self, rspecifier, wspecifier, minibatch_size=16):
+        """Aligns every example of an egs archive to its own labels and writes
+        the Int32Vector table `wspecifier` (kctc_nnet_align_egs) ->
+        dict(num_done, num_infeasible, tot_score, tot_frames)."""
+        nd, ni, fr, sc = ctypes.c_long(), ctypes.c_long(), ctypes.c_long(), ctypes.c_double()
+        _tcheck(lib().kctc_nnet_align_egs(self.h, str(rspecifier).encode(), str(wspecifier).encode(),
+                                          int(minibatch_size), ctypes.byref(nd), ctypes.byref(ni), ctypes.byref(sc),
+                                          ctypes.byref(fr)), "nnet_align_egs")
+        return dict(num_done=nd.value, num_infeasible=ni.value, tot_score=sc.value, tot_frames=fr.value)
 
     def adjust_priors(self, posterior_sum=None, google_prior_const=0.0):
         """nnet-adjust-priors: priors = posterior_sum / its total, or (with

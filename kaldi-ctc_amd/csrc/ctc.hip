@@ -36,23 +36,17 @@
 
 #include "common.h"
 #include "ctc.h"
+#include "ctc_shared.h"
 #include "prof.h"
 
 namespace kctc {
 namespace ctcimpl {
 
-constexpr int kMaxLabel = 639;  // MAX_WARPCTC_LABEL_LENGTH, src/ctc/ctc-nnet-train.cc:25-26
 constexpr int kThreads = 256;  // K3
 constexpr int kABThreads = 512;  // K2: 8 waves, 2 per SIMD, <= 3 states per thread
 constexpr int kABWaves = kABThreads / 64;
 constexpr int kSPT = (2 * kMaxLabel + 1 + kABThreads - 1) / kABThreads;  // states per thread (3)
 constexpr int kFR = 8;   // frames per K3 workgroup
-
-struct UttDesc {
-  int T, L, S, feasible, lab_off, pad;
-  long long ab_off;   // float offset of this utterance's alpha spill; beta follows at +T*S
-  long long off_off;  // double offset of offA[T]; offB follows at +T
-};
 
 struct Layout {
   size_t desc, labels, links, owner, costs, logz, lp, spill, offs, total;
@@ -120,6 +114,11 @@ __global__ __launch_bounds__(256) void ctc_logz(const float *__restrict__ acts, 
   for (int a = lane; a < A; a += kWave) lp[row * A + a] = r[a] - z;  // normalised log-probs (K2 input)
 }
 
+void launch_logz(const float *acts, int A, long rows, float *logz, float *lp, hipStream_t stream) {
+  ProfSpan ps(stream, "ctc_logz");
+  hipLaunchKernelGGL(ctc_logz, dim3(ceil_div(rows, 4)), dim3(256), 0, stream, acts, A, rows, logz, lp);
+}
+
 // log(e^a + e^b + e^c) as max + log1p(sum of the two smaller terms): the
 // dominant term contributes exactly 1, so log1p keeps full relative precision
 // of the small ones (logf(1 + x) would round x to the ulp of 1).  log1p(x) is
@@ -160,12 +159,6 @@ struct AbLds {
   int pair;  // frames per barrier of the window kernel (1..8): mictc_set_frame_group
   size_t floats(int waves) const { return 2 * (size_t)F * SP + 2 * (size_t)CP + 2 * waves + 4; }
 };
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // ---------------------------------------------------------------------------
 // K2, long label sequences (launched for more states than the window kernel's
@@ -606,7 +599,7 @@ struct Staging {
 };
 static thread_local Staging g_stage;
 
-static char *staging_acquire(size_t bytes) {
+char *staging_acquire(size_t bytes) {
   Staging &s = g_stage;
   if (s.pending) {
     if (hipEventSynchronize(s.ev) != hipSuccess) return nullptr;
@@ -624,7 +617,7 @@ static char *staging_acquire(size_t bytes) {
   }
   return s.buf;
 }
-static void staging_release(hipStream_t stream) {
+void staging_release(hipStream_t stream) {
   if (hipEventRecord(g_stage.ev, stream) == hipSuccess) g_stage.pending = true;
 }
 
@@ -703,11 +696,7 @@ static ctcStatus_t launch(const Layout &lay, const std::vector<UttDesc> &descs, 
   double *d_offs = reinterpret_cast<double *>(ws + lay.offs);
   const long rows = (long)lay.T_max * N;
   float *d_lp = reinterpret_cast<float *>(ws + lay.lp);
-  if (rows > 0) {
-    ProfSpan ps(stream, "ctc_logz");
-    hipLaunchKernelGGL(ctc_logz, dim3(ceil_div(rows, 4)), dim3(256), 0, stream, acts, A, rows,
-                       d_logz, d_lp);
-  }
+  if (rows > 0) launch_logz(acts, A, rows, d_logz, d_lp, stream);
   const bool want = grads != nullptr;
   const int Lmax = lay.L_max, Smax = 2 * Lmax + 1;
   const ctcStatus_t st = launch_alpha_beta(Smax, want, d_lp, N, A, blank, d_desc, d_lab, d_spill, d_offs,

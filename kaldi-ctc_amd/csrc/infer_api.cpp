@@ -1,12 +1,16 @@
 // infer_api.cpp -- C ABI of include/kaldi_ctc_decode.h and the forward-only
 // entry points of kaldi_ctc_train.h: propagate, the CTC decodable (one
-// utterance and batched), posterior sums, priors and compute-prob.
+// utterance and batched), posterior sums, priors, compute-prob and the CTC
+// forced alignment of a batch or an egs archive.
 #include "kaldi_ctc_decode.h"
 
+#include <fstream>
 #include <vector>
 
+#include "ctc.h"
 #include "decodable.h"
 #include "elementwise.h"
+#include "kaldi_io.h"
 #include "nnet_handle.h"
 #include "seq_align.h"
 
@@ -60,7 +64,114 @@ static long for_each_batch(const char *rspecifier, size_t batch_size, F fn) {
   return ne;
 }
 
+// kctc_nnet_align on a formatted input: variable-length forward, then the
+// alignment of the un-normalised activations on the network's stream
+static void align_batch(kctcNnet_t n, const float *feats_dev, int T_max, int N, const int *num_frames,
+                        const int *flat_labels, const int *label_lengths, int *ali_host, double *scores_host) {
+  KCTC_REQUIRE(N >= 1 && N <= kctc::kSeqMaxN, "kctc_nnet_align: N outside [1, 64]");
+  n->evaluator.ForwardSeq(feats_dev, T_max, N, num_frames);
+  // a final SoftmaxComponent (the recipe's final.mdl) only shifts every row's
+  // log by a constant, which the alignment's own normaliser removes: align on its input
+  const int C = n->nnet.NumComponents();
+  const bool softmax = dynamic_cast<const kctc::nnet2::SoftmaxComponent *>(&n->nnet.GetComponent(C - 1)) != nullptr;
+  const auto &o = n->evaluator.InputOf(softmax ? C - 1 : C);
+  const int A = o.NumCols();
+  const size_t rows = (size_t)T_max * N;
+  size_t ws = 0;
+  // CTC input lengths: NumFrames - ignore_frames, 0 ignored here as in the updater
+  ctcStatus_t st = mictc_get_align_workspace_size(label_lengths, num_frames, A, N, &ws);
+  if (st != CTC_STATUS_SUCCESS)
+    throw std::invalid_argument(std::string("mictc_get_align_workspace_size: ") + ctcGetStatusString(st));
+  n->ali_ws.ensure(ws);
+  n->ali_ids.ensure(sizeof(int) * rows);
+  n->ali_scores.ensure(sizeof(double) * N);
+  int *ids = static_cast<int *>(n->ali_ids.p);
+  // the alignment fills rows below max(num_frames); T_max may be longer
+  KCTC_HIP_CHECK(hipMemsetAsync(ids, 0xFF, sizeof(int) * rows, n->stream));
+  st = mictc_ctc_align_async(o.Data(), flat_labels, label_lengths, num_frames, A, N, ids,
+                             static_cast<double *>(n->ali_scores.p), n->ali_ws.p,
+                             reinterpret_cast<ctcStream_t>(n->stream), 0);
+  if (st != CTC_STATUS_SUCCESS)
+    throw std::invalid_argument(std::string("mictc_ctc_align_async: ") + ctcGetStatusString(st));
+  KCTC_HIP_CHECK(hipMemcpyAsync(ali_host, ids, sizeof(int) * rows, hipMemcpyDeviceToHost, n->stream));
+  KCTC_HIP_CHECK(hipMemcpyAsync(scores_host, n->ali_scores.p, sizeof(double) * N, hipMemcpyDeviceToHost, n->stream));
+  KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+}
+
 extern "C" {
+
+int kctc_nnet_align(kctcNnet_t n, const float *feats_dev, int T_max, int N, const int *num_frames,
+                    const int *flat_labels, const int *label_lengths, int *ali_host, double *scores_host) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && feats_dev && num_frames && flat_labels && label_lengths && ali_host && scores_host,
+                 "kctc_nnet_align: null argument");
+    n->activate();
+    align_batch(n, feats_dev, T_max, N, num_frames, flat_labels, label_lengths, ali_host, scores_host);
+    collect_profile(n);
+  });
+}
+
+int kctc_nnet_align_egs(kctcNnet_t n, const char *egs_rspecifier, const char *ali_wspecifier, int minibatch_size,
+                        long *num_done, long *num_infeasible, double *tot_score, long *tot_frames) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && egs_rspecifier && ali_wspecifier, "kctc_nnet_align_egs: null argument");
+    KCTC_REQUIRE(minibatch_size >= 1 && minibatch_size <= kctc::kSeqMaxN,
+                 "kctc_nnet_align_egs: minibatch_size outside [1, 64]");
+    std::string path = ali_wspecifier;
+    const auto colon = path.find(':');
+    if (colon != std::string::npos) {
+      KCTC_REQUIRE(path.compare(0, 3, "ark") == 0, "kctc_nnet_align_egs: only ark: specifiers are supported");
+      path = path.substr(colon + 1);
+    }
+    n->activate();
+    std::ofstream os(path, std::ios::binary | std::ios::trunc);
+    if (!os) throw std::runtime_error("cannot write alignment archive " + path);
+    long done = 0, infeasible = 0, frames = 0;
+    double score = 0.0;
+    std::vector<int> ids;
+    std::vector<double> scores;
+    for_each_batch(egs_rspecifier, minibatch_size, [&](std::vector<kctc::egs::Example> &batch) {
+      // every example from its own start offset, pad_input = false (as kctc_nnet_sum_posteriors)
+      std::unique_ptr<kctc::egs::Minibatch> mb =
+          kctc::egs::pack_minibatch(batch, n->nnet.LeftContext(), n->nnet.RightContext(), true);
+      n->check_input_dim(*mb);
+      kctc::SeqLens lens;
+      if (!kctc::seq_lens(mb->num_frames.data(), mb->T_max, mb->N, &lens))
+        throw std::invalid_argument("an example is shorter than the network's context");
+      n->stage_minibatch(*mb);
+      const int N = mb->N, T_max = mb->T_max;
+      ids.resize((size_t)T_max * N);
+      scores.resize(N);
+      const int none = 0;  // a batch without labels still passes a valid pointer
+      align_batch(n, n->egs_feats.f(), T_max, N, mb->num_frames.data(), mb->labels.empty() ? &none : mb->labels.data(),
+                  mb->label_lengths.data(), ids.data(), scores.data());
+      for (int u = 0; u < N; u++) {
+        if (ids[u] < 0) {  // frame 0 of an infeasible utterance is -1
+          infeasible++;
+          continue;
+        }
+        const int T = mb->num_frames[u];
+        std::vector<int32_t> v((size_t)T);
+        for (int t = 0; t < T; t++) v[t] = ids[(size_t)t * N + u];
+        // Kaldi table entry: "<key> " then the binary marker and the Int32Vector
+        os << mb->keys[u] << ' ';
+        os.put('\0');
+        os.put('B');
+        kctc::kio::WriteIntVector(os, true, v);
+        done++;
+        frames += T;
+        score += scores[u];
+      }
+    });
+    os.flush();
+    if (!os) throw std::runtime_error("error writing alignment archive " + path);
+    collect_profile(n);
+    if (num_done) *num_done = done;
+    if (num_infeasible) *num_infeasible = infeasible;
+    if (tot_score) *tot_score = score;
+    if (tot_frames) *tot_frames = frames;
+  });
+}
 
 size_t kctc_ctc_decodable_scratch_bytes(int T) { return kctc::ctc_decodable_scratch_bytes(T > 0 ? T : 1) + 256; }
 

@@ -739,6 +739,8 @@ class NnetCtcUpdater {
   const std::vector<double> &LastCosts() const { return last_costs_; }
   // network output of the last minibatch queued (device, [T_max*N][A])
   const CuMatrixBase &Output() const { return forward_data_.empty() ? empty_ : forward_data_.back(); }
+  // input of component c in the last forward (c = NumComponents(): the output)
+  const CuMatrixBase &InputOf(int c) const { return forward_data_.at(c); }
   // srand(seed) of the process stream (nnet2-ctc-train-simple.cc:47,69;
   // default 0) that ClipGradient self-repair draws from
   void Srand(unsigned seed) { repair_rng_.Seed(seed); }

@@ -63,6 +63,8 @@ struct kctcNnetImpl : kctcStreams {
   // batch gathered for a spliced network, the per-utterance row counts, the
   // fp64 column sums and their slab partials
   kctc::nnet2::DevBuf dec_gather, dec_kept, post_sum, post_scratch;
+  // forced alignment (kctc_nnet_align): workspace, frame ids, path scores
+  kctc::nnet2::DevBuf ali_ws, ali_ids, ali_scores;
   // nnet2-ctc model file extras: the CtcTransitionModel exactly as read (opaque
   // bytes, in the mode of the file it came from) and AmNnet's priors
   std::string trans_model;
