@@ -139,6 +139,47 @@ ctcStatus_t mictc_ctc_align_async(const float *activations, const int *flat_labe
  * previous value; on < 0 only queries. */
 int mictc_set_align_kernel(int on);
 
+/* ---- CTC prefix beam search (lexicon-free; csrc/ctc_beam.hip) --------------
+ * The most likely transcript of each utterance among the prefixes a beam
+ * keeps.  With lp[t][a] the log-softmax of frame t, a prefix p (a sequence of
+ * non-blank labels, last label e) carries over frames 0..t
+ *   b(p):  log-prob of the alignments that collapse to p and end in blank,
+ *   nb(p): the same for those that end in a label;  tot = b (+) nb (log-add).
+ * Before frame 0 the beam holds the empty prefix with b = 0, nb = -inf.
+ * Frame t, with C_t the K = min(symbols, alphabet_size - 1) non-blank symbols
+ * of largest lp[t][c] (ties to the lower id):
+ *   stay    b'(p)  (+)= lp[t][blank] + tot(p);
+ *           nb'(p) (+)= lp[t][e] + nb(p)                      (p non-empty);
+ *   extend  nb'(p+c) (+)= lp[t][c] + (c == e ? b(p) : tot(p))  for c in C_t;
+ *   merge   prefixes that are equal as label sequences are one entry and their
+ *           contributions add (p+c may already be in the beam);
+ *   prune   the `beam` entries of largest tot' stay (ties: deterministic).
+ * The result is the entry of largest tot after the last frame.
+ *  - activations [maxT][minibatch][alphabet_size] float, DEVICE, un-normalised,
+ *    maxT = max(input_lengths); rows t >= input_lengths[n] are never read.
+ *  - input_lengths: HOST, consumed before return; each in [0, maxT].
+ *  - hyp_dev int [minibatch][maxT], DEVICE: row n holds the labels of
+ *    utterance n, then -1.  hyp_len_dev int [minibatch]: their number.
+ *  - scores_dev double [minibatch], DEVICE: tot of the result.  It is a lower
+ *    bound of the CTC log-probability of the returned labels (pruning only
+ *    drops mass) and equal to it when nothing was pruned.
+ *  - An utterance with T == 0 gives length 0 and score 0.
+ *  - workspace: DEVICE, >= mictc_get_beam_workspace_size() bytes (the
+ *    normalised log-probs and 16 bytes per frame and beam entry of prefix
+ *    nodes).
+ * 1 <= beam <= 128, 1 <= symbols <= 64, alphabet_size >= 2,
+ * 0 <= blank_label < alphabet_size; anything else, a negative length or a
+ * null pointer returns CTC_STATUS_INVALID_VALUE and enqueues nothing.
+ * Stream-ordered: never synchronises, allocates no device memory.
+ * Deterministic (no atomics): two calls give identical bytes. */
+ctcStatus_t mictc_get_beam_workspace_size(const int *input_lengths, int alphabet_size, int minibatch,
+                                          int beam, size_t *size_bytes);
+ctcStatus_t mictc_ctc_beam_search_async(const float *activations, const int *input_lengths,
+                                        int alphabet_size, int minibatch, int beam, int symbols,
+                                        int *hyp_dev /* [minibatch][maxT], -1 padded */,
+                                        int *hyp_len_dev /* [minibatch] */, double *scores_dev /* [minibatch] */,
+                                        void *workspace, ctcStream_t stream, int blank_label);
+
 #ifdef __cplusplus
 }
 #endif

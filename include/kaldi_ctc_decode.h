@@ -26,6 +26,9 @@
  *                            <- CTC forced alignment of a batch / an egs archive
  *                               (an extension; writes the Int32Vector table that
  *                               nnet-ctc-relabel-egs reads)
+ *   kctc_nnet_decode / kctc_nnet_decode_egs
+ *                            <- lexicon-free CTC prefix beam search of a batch /
+ *                               an egs archive (an extension; no WFST)
  * Return 0 on success (kctc_last_error() describes a failure).
  */
 #ifndef KALDI_CTC_AMD_KALDI_CTC_DECODE_H_
@@ -171,6 +174,30 @@ int kctc_nnet_align(kctcNnet_t nnet, const float *feats_dev, int T_max, int N, c
  * and of their frames. */
 int kctc_nnet_align_egs(kctcNnet_t nnet, const char *egs_rspecifier, const char *ali_wspecifier,
                         int minibatch_size, long *num_done, long *num_infeasible, double *tot_score, long *tot_frames);
+
+/* ---- CTC prefix beam search (an extension; the kernels and the recursion: ctc.h) ----
+ * kctc_nnet_decode: the most likely label sequence of every utterance that a
+ * beam of `beam` (1..128) prefixes finds, each frame extending by its
+ * `symbols` (1..64) most likely labels.  feats_dev, T_max, N, num_frames as for
+ * kctc_nnet_propagate_seq (N <= 64): the variable-length forward, so every
+ * utterance is decoded as if it were run alone, then
+ * mictc_ctc_beam_search_async on the network's stream with blank 0.  Like the
+ * alignment it runs on un-normalised activations: of a network that ends in a
+ * SoftmaxComponent, on that component's input.  No priors, no prob-scale, no
+ * lexicon.  hyp_host: N*T_max ints, row n the labels of utterance n (symbol
+ * ids, label = pdf + 1) then -1; hyp_len_host: N ints; scores_host: N doubles,
+ * the log-probability the beam holds for each result. */
+int kctc_nnet_decode(kctcNnet_t nnet, const float *feats_dev, int T_max, int N, const int *num_frames, int beam,
+                     int symbols, int *hyp_host, int *hyp_len_host, double *scores_host);
+
+/* Decodes every example of an egs archive (read as kctc_nnet_align_egs reads
+ * it) and writes, per example key, the hypothesis as a Kaldi Int32Vector to a
+ * binary "ark:".  Outputs (nullable): examples decoded, the sum of their own
+ * label counts and the sum of LevenshteinEditDistance(labels, hypothesis), so
+ * that 1 - edit_distance / num_labels compares with kctc_nnet_compute_prob's
+ * best-path accuracy. */
+int kctc_nnet_decode_egs(kctcNnet_t nnet, const char *egs_rspecifier, const char *hyp_wspecifier, int minibatch_size,
+                         int beam, int symbols, long *num_utts, long *num_labels, long *edit_distance);
 
 #ifdef __cplusplus
 }

@@ -225,6 +225,46 @@ def ctc_align(acts, flat_labels, label_lengths, input_lengths, blank=0, stream=N
     return ali, scores.cpu().numpy()
 
 
+def ctc_beam_workspace_size(input_lengths, alphabet_size, beam):
+    il = np.ascontiguousarray(input_lengths, dtype=np.int32)
+    out = ctypes.c_size_t()
+    st = lib().mictc_get_beam_workspace_size(il.ctypes.data, int(alphabet_size), len(il), int(beam),
+                                             ctypes.byref(out))
+    if st != 0:
+        raise CtcError(st, "mictc_get_beam_workspace_size")
+    return out.value
+
+
+def ctc_beam_search(acts, input_lengths, beam=16, symbols=40, blank=0, stream=None, workspace=None):
+    """Lexicon-free CTC prefix beam search (mictc_ctc_beam_search_async) of a
+    torch CUDA tensor acts [T, N, A] (float32, un-normalised): `beam` prefixes,
+    each frame extending by its `symbols` most likely labels.  Returns (hyps:
+    list of N int lists, the most likely label sequence the beam found for
+    each utterance; scores np.float64 [N]: the log-probability the beam holds
+    for it, a lower bound of its CTC log-probability)."""
+    import torch
+    assert acts.is_cuda and acts.dtype == torch.float32 and acts.is_contiguous()
+    T, N, A = acts.shape
+    il = np.ascontiguousarray(input_lengths, dtype=np.int32)
+    if len(il) != N or (N and int(il.max()) > T):
+        raise CtcError(2, "ctc_beam_search")
+    if workspace is None:
+        workspace = torch.empty(ctc_beam_workspace_size(il, A, beam), dtype=torch.uint8, device=acts.device)
+    max_t = int(il.max()) if N else 0
+    hyp = torch.empty((N, max(max_t, 1)), dtype=torch.int32, device=acts.device)
+    hyp_len = torch.empty(N, dtype=torch.int32, device=acts.device)
+    scores = torch.empty(N, dtype=torch.float64, device=acts.device)
+    st = lib().mictc_ctc_beam_search_async(acts.data_ptr(), il.ctypes.data, A, N, int(beam), int(symbols),
+                                           hyp.data_ptr(), hyp_len.data_ptr(), scores.data_ptr(),
+                                           workspace.data_ptr(), _stream_handle(stream), blank)
+    if st != 0:
+        raise CtcError(st, "mictc_ctc_beam_search_async")
+    if stream is not None:
+        torch.cuda.synchronize()  # the copies below run on the current stream
+    hyp, hyp_len = hyp.cpu().numpy().reshape(-1), hyp_len.cpu().numpy()
+    return [hyp[n * max_t:n * max_t + int(hyp_len[n])].tolist() for n in range(N)], scores.cpu().numpy()
+
+
 def read_int_vector_ark(path):
     """Binary Kaldi archive of Int32Vector (what Nnet.align_egs writes and
     ali-to-post reads) -> dict key -> np.int32 array, in archive order."""
@@ -907,6 +947,33 @@ class Nnet:
                                           int(minibatch_size), ctypes.byref(nd), ctypes.byref(ni), ctypes.byref(sc),
                                           ctypes.byref(fr)), "nnet_align_egs")
         return dict(num_done=nd.value, num_infeasible=ni.value, tot_score=sc.value, tot_frames=fr.value)
+
+    def decode(self, feats, T, N, num_frames, beam=16, symbols=40):
+        """Lexicon-free CTC prefix beam search of a variable-length batch
+        (kctc_nnet_decode; feats as for train_step, N <= 64, every utterance as
+        if run alone) -> (hyps: list of N int lists of symbol ids, blank 0
+        never among them; scores np.float64 [N])."""
+        self._check_feats(feats, T, N)
+        nf = np.ascontiguousarray(num_frames, dtype=np.int32)
+        if len(nf) != N:
+            raise KctcError("decode: num_frames must have N entries")
+        hyp = np.empty((N, T), np.int32)
+        hyp_len = np.empty(N, np.int32)
+        scores = np.empty(N, np.float64)
+        _tcheck(lib().kctc_nnet_decode(self.h, _ptr(feats), T, N, nf.ctypes.data, int(beam), int(symbols),
+                                       hyp.ctypes.data, hyp_len.ctypes.data, scores.ctypes.data), "nnet_decode")
+        return [hyp[n, :hyp_len[n]].tolist() for n in range(N)], scores
+
+    def decode_egs(self, rspecifier, wspecifier, minibatch_size=16, beam=16, symbols=40):
+        """Decodes every example of an egs archive and writes the hypotheses as
+        the Int32Vector table `wspecifier` (kctc_nnet_decode_egs) ->
+        (num_utts, num_labels, edit_distance): 1 - edit_distance / num_labels
+        compares with compute_prob's best-path accuracy."""
+        nu, nl, ed = ctypes.c_long(), ctypes.c_long(), ctypes.c_long()
+        _tcheck(lib().kctc_nnet_decode_egs(self.h, str(rspecifier).encode(), str(wspecifier).encode(),
+                                           int(minibatch_size), int(beam), int(symbols), ctypes.byref(nu),
+                                           ctypes.byref(nl), ctypes.byref(ed)), "nnet_decode_egs")
+        return nu.value, nl.value, ed.value
 
     def adjust_priors(self, posterior_sum=None, google_prior_const=0.0):
         """nnet-adjust-priors: priors = posterior_sum / its total, or (with

@@ -1,5 +1,6 @@
-// ctc_shared.h -- what the CTC loss (ctc.hip) and the CTC forced alignment
-// (ctc_align.hip) share: the utterance descriptor, the LDS-only barrier of the
+// ctc_shared.h -- what the CTC loss (ctc.hip), the CTC forced alignment
+// (ctc_align.hip) and the CTC prefix beam search (ctc_beam.hip) share: the
+// utterance descriptor, the LDS-only barrier of the
 // serial frame loops, the per-frame normaliser's launch and the pinned staging
 // buffer of the host arrays.  Private to csrc/.
 #pragma once
@@ -16,6 +17,7 @@ struct UttDesc {
   int T, L, S, feasible, lab_off, pad;
   long long ab_off;   // loss: float offset of this utterance's alpha spill; beta follows at +T*S
                       // alignment: offset, in 16-byte words, of its back-pointer spill
+                      // beam search: offset, in 16-byte nodes, of its prefix node pool
   long long off_off;  // loss: double offset of offA[T]; offB follows at +T (alignment: unused)
 };
 

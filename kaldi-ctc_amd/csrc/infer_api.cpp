@@ -1,10 +1,12 @@
 // infer_api.cpp -- C ABI of include/kaldi_ctc_decode.h and the forward-only
 // entry points of kaldi_ctc_train.h: propagate, the CTC decodable (one
-// utterance and batched), posterior sums, priors, compute-prob and the CTC
-// forced alignment of a batch or an egs archive.
+// utterance and batched), posterior sums, priors, compute-prob, and the CTC
+// forced alignment and prefix beam search of a batch or an egs archive.
 #include "kaldi_ctc_decode.h"
 
+#include <algorithm>
 #include <fstream>
+#include <string>
 #include <vector>
 
 #include "ctc.h"
@@ -64,17 +66,138 @@ static long for_each_batch(const char *rspecifier, size_t batch_size, F fn) {
   return ne;
 }
 
+// file name of a binary "ark:" wspecifier (a bare file name passes)
+static std::string ark_path(const char *wspecifier) {
+  std::string path = wspecifier;
+  const auto colon = path.find(':');
+  if (colon != std::string::npos) {
+    KCTC_REQUIRE(path.compare(0, 3, "ark") == 0, "only ark: specifiers are supported");
+    path = path.substr(colon + 1);
+  }
+  return path;
+}
+
+// Kaldi table entry: "<key> " then the binary marker and the Int32Vector
+static void write_int_vector_entry(std::ostream &os, const std::string &key, const std::vector<int32_t> &v) {
+  os << key << ' ';
+  os.put('\0');
+  os.put('B');
+  kctc::kio::WriteIntVector(os, true, v);
+}
+
+// The un-normalised activations of the last forward: a final SoftmaxComponent
+// (the recipe's final.mdl) only shifts every row's log by a constant, which
+// the CTC kernels' own normaliser removes, so they run on its input.
+static const kctc::nnet2::CuMatrixBase &unnormalised_output(kctcNnet_t n) {
+  const int C = n->nnet.NumComponents();
+  const bool softmax = dynamic_cast<const kctc::nnet2::SoftmaxComponent *>(&n->nnet.GetComponent(C - 1)) != nullptr;
+  return n->evaluator.InputOf(softmax ? C - 1 : C);
+}
+
+// kctc_nnet_decode on a formatted input: variable-length forward, then the
+// prefix beam search on the network's stream; hyp_host is [N][T_max]
+static void decode_batch(kctcNnet_t n, const float *feats_dev, int T_max, int N, const int *num_frames, int beam,
+                         int symbols, int *hyp_host, int *hyp_len_host, double *scores_host) {
+  KCTC_REQUIRE(N >= 1 && N <= kctc::kSeqMaxN, "kctc_nnet_decode: N outside [1, 64]");
+  n->evaluator.ForwardSeq(feats_dev, T_max, N, num_frames);
+  const auto &o = unnormalised_output(n);
+  const int A = o.NumCols();
+  int maxT = 0;
+  for (int u = 0; u < N; u++) maxT = std::max(maxT, num_frames[u]);
+  size_t ws = 0;
+  ctcStatus_t st = mictc_get_beam_workspace_size(num_frames, A, N, beam, &ws);
+  if (st != CTC_STATUS_SUCCESS)
+    throw std::invalid_argument(std::string("mictc_get_beam_workspace_size: ") + ctcGetStatusString(st));
+  n->beam_ws.ensure(ws);
+  n->beam_hyp.ensure(sizeof(int) * (size_t)maxT * N);
+  n->beam_len.ensure(sizeof(int) * N);
+  n->beam_scores.ensure(sizeof(double) * N);
+  st = mictc_ctc_beam_search_async(o.Data(), num_frames, A, N, beam, symbols, static_cast<int *>(n->beam_hyp.p),
+                                   static_cast<int *>(n->beam_len.p), static_cast<double *>(n->beam_scores.p),
+                                   n->beam_ws.p, reinterpret_cast<ctcStream_t>(n->stream), 0);
+  if (st != CTC_STATUS_SUCCESS)
+    throw std::invalid_argument(std::string("mictc_ctc_beam_search_async: ") + ctcGetStatusString(st));
+  // the search fills max(num_frames) columns; T_max may be longer
+  std::fill(hyp_host, hyp_host + (size_t)T_max * N, -1);
+  if (maxT > 0)
+    KCTC_HIP_CHECK(hipMemcpy2DAsync(hyp_host, sizeof(int) * T_max, n->beam_hyp.p, sizeof(int) * maxT,
+                                    sizeof(int) * maxT, N, hipMemcpyDeviceToHost, n->stream));
+  KCTC_HIP_CHECK(hipMemcpyAsync(hyp_len_host, n->beam_len.p, sizeof(int) * N, hipMemcpyDeviceToHost, n->stream));
+  KCTC_HIP_CHECK(hipMemcpyAsync(scores_host, n->beam_scores.p, sizeof(double) * N, hipMemcpyDeviceToHost, n->stream));
+  KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+}
+
+extern "C" {
+
+int kctc_nnet_decode(kctcNnet_t n, const float *feats_dev, int T_max, int N, const int *num_frames, int beam,
+                     int symbols, int *hyp_host, int *hyp_len_host, double *scores_host) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && feats_dev && num_frames && hyp_host && hyp_len_host && scores_host,
+                 "kctc_nnet_decode: null argument");
+    n->activate();
+    decode_batch(n, feats_dev, T_max, N, num_frames, beam, symbols, hyp_host, hyp_len_host, scores_host);
+    collect_profile(n);
+  });
+}
+
+int kctc_nnet_decode_egs(kctcNnet_t n, const char *egs_rspecifier, const char *hyp_wspecifier, int minibatch_size,
+                         int beam, int symbols, long *num_utts, long *num_labels, long *edit_distance) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && egs_rspecifier && hyp_wspecifier, "kctc_nnet_decode_egs: null argument");
+    KCTC_REQUIRE(minibatch_size >= 1 && minibatch_size <= kctc::kSeqMaxN,
+                 "kctc_nnet_decode_egs: minibatch_size outside [1, 64]");
+    const std::string path = ark_path(hyp_wspecifier);
+    n->activate();
+    std::ofstream os(path, std::ios::binary | std::ios::trunc);
+    if (!os) throw std::runtime_error("cannot write hypothesis archive " + path);
+    long utts = 0, labels = 0, errs = 0;
+    std::vector<int> hyp, hyp_len;
+    std::vector<double> scores;
+    for_each_batch(egs_rspecifier, minibatch_size, [&](std::vector<kctc::egs::Example> &batch) {
+      // every example from its own start offset, pad_input = false (as kctc_nnet_sum_posteriors)
+      std::unique_ptr<kctc::egs::Minibatch> mb =
+          kctc::egs::pack_minibatch(batch, n->nnet.LeftContext(), n->nnet.RightContext(), true);
+      n->check_input_dim(*mb);
+      kctc::SeqLens lens;
+      if (!kctc::seq_lens(mb->num_frames.data(), mb->T_max, mb->N, &lens))
+        throw std::invalid_argument("an example is shorter than the network's context");
+      n->stage_minibatch(*mb);
+      const int N = mb->N, T_max = mb->T_max;
+      hyp.resize((size_t)T_max * N);
+      hyp_len.resize(N);
+      scores.resize(N);
+      decode_batch(n, n->egs_feats.f(), T_max, N, mb->num_frames.data(), beam, symbols, hyp.data(), hyp_len.data(),
+                   scores.data());
+      size_t lab_off = 0;
+      for (int u = 0; u < N; u++) {
+        const int *h = hyp.data() + (size_t)u * T_max;
+        const int L = mb->label_lengths[u];
+        write_int_vector_entry(os, mb->keys[u], std::vector<int32_t>(h, h + hyp_len[u]));
+        // LevenshteinEditDistance to the example's own labels, as compute_prob's accuracy counts it
+        errs += kctc::nnet2::levenshtein(mb->labels.data() + lab_off, L, h, hyp_len[u]);
+        lab_off += L;
+        labels += L;
+        utts++;
+      }
+    });
+    os.flush();
+    if (!os) throw std::runtime_error("error writing hypothesis archive " + path);
+    collect_profile(n);
+    if (num_utts) *num_utts = utts;
+    if (num_labels) *num_labels = labels;
+    if (edit_distance) *edit_distance = errs;
+  });
+}
+
+}  // extern "C"
+
 // kctc_nnet_align on a formatted input: variable-length forward, then the
 // alignment of the un-normalised activations on the network's stream
 static void align_batch(kctcNnet_t n, const float *feats_dev, int T_max, int N, const int *num_frames,
                         const int *flat_labels, const int *label_lengths, int *ali_host, double *scores_host) {
   KCTC_REQUIRE(N >= 1 && N <= kctc::kSeqMaxN, "kctc_nnet_align: N outside [1, 64]");
   n->evaluator.ForwardSeq(feats_dev, T_max, N, num_frames);
-  // a final SoftmaxComponent (the recipe's final.mdl) only shifts every row's
-  // log by a constant, which the alignment's own normaliser removes: align on its input
-  const int C = n->nnet.NumComponents();
-  const bool softmax = dynamic_cast<const kctc::nnet2::SoftmaxComponent *>(&n->nnet.GetComponent(C - 1)) != nullptr;
-  const auto &o = n->evaluator.InputOf(softmax ? C - 1 : C);
+  const auto &o = unnormalised_output(n);
   const int A = o.NumCols();
   const size_t rows = (size_t)T_max * N;
   size_t ws = 0;
@@ -117,12 +240,7 @@ int kctc_nnet_align_egs(kctcNnet_t n, const char *egs_rspecifier, const char *al
     KCTC_REQUIRE(n && egs_rspecifier && ali_wspecifier, "kctc_nnet_align_egs: null argument");
     KCTC_REQUIRE(minibatch_size >= 1 && minibatch_size <= kctc::kSeqMaxN,
                  "kctc_nnet_align_egs: minibatch_size outside [1, 64]");
-    std::string path = ali_wspecifier;
-    const auto colon = path.find(':');
-    if (colon != std::string::npos) {
-      KCTC_REQUIRE(path.compare(0, 3, "ark") == 0, "kctc_nnet_align_egs: only ark: specifiers are supported");
-      path = path.substr(colon + 1);
-    }
+    const std::string path = ark_path(ali_wspecifier);
     n->activate();
     std::ofstream os(path, std::ios::binary | std::ios::trunc);
     if (!os) throw std::runtime_error("cannot write alignment archive " + path);
@@ -153,11 +271,7 @@ int kctc_nnet_align_egs(kctcNnet_t n, const char *egs_rspecifier, const char *al
         const int T = mb->num_frames[u];
         std::vector<int32_t> v((size_t)T);
         for (int t = 0; t < T; t++) v[t] = ids[(size_t)t * N + u];
-        // Kaldi table entry: "<key> " then the binary marker and the Int32Vector
-        os << mb->keys[u] << ' ';
-        os.put('\0');
-        os.put('B');
-        kctc::kio::WriteIntVector(os, true, v);
+        write_int_vector_entry(os, mb->keys[u], v);
         done++;
         frames += T;
         score += scores[u];

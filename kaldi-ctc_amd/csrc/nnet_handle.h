@@ -65,6 +65,8 @@ struct kctcNnetImpl : kctcStreams {
   kctc::nnet2::DevBuf dec_gather, dec_kept, post_sum, post_scratch;
   // forced alignment (kctc_nnet_align): workspace, frame ids, path scores
   kctc::nnet2::DevBuf ali_ws, ali_ids, ali_scores;
+  // prefix beam search (kctc_nnet_decode): workspace, hypotheses, their lengths, scores
+  kctc::nnet2::DevBuf beam_ws, beam_hyp, beam_len, beam_scores;
   // nnet2-ctc model file extras: the CtcTransitionModel exactly as read (opaque
   // bytes, in the mode of the file it came from) and AmNnet's priors
   std::string trans_model;
