@@ -1535,3 +1535,146 @@ class EgsReader:
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------
+# LDA feature transform (include/kaldi_lda.h): get_lda.sh inside the project
+# ---------------------------------------------------------------------------
+LDA_BLANK_SKIP, LDA_BLANK_CLASS, LDA_BLANK_FILL = 0, 1, 2
+_LDA_POLICY = {"skip": LDA_BLANK_SKIP, "class": LDA_BLANK_CLASS, "fill": LDA_BLANK_FILL}
+
+
+def _f64(a, shape, what):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError(f"{what}: shape {a.shape}, expected {shape}")
+    return a
+
+
+def _lda_result(dim, D, remove_offset, want_cholesky):
+    rows = D if dim <= 0 else dim
+    M = np.empty((max(rows, 0), D + (1 if remove_offset else 0)), np.float32)
+    chol = np.empty((D, D), np.float64) if want_cholesky else None
+    return M, chol
+
+
+def estimate_feature_transform(zero, first, second, dim=-1, within_class_factor=0.001, remove_offset=True,
+                               max_singular_value=5.0, want_cholesky=True):
+    """nnet-get-feature-transform from host statistics (kctc_lda_estimate_from_stats;
+    no device): zero [C], first [C][D], second [D][D] (read through its lower
+    triangle) -> (M float32 [dim][D (+1 with remove_offset)], the lower-triangular
+    Cholesky factor of the within-class covariance, or None)."""
+    first = np.ascontiguousarray(first, dtype=np.float64)
+    if first.ndim != 2:
+        raise ValueError("estimate_feature_transform: first must be [C][D]")
+    C, D = first.shape
+    zero = _f64(zero, (C,), "zero")
+    second = _f64(second, (D, D), "second")
+    if dim > D:
+        raise KctcError("kctc_lda_estimate_from_stats: output dimension above the feature dimension")
+    M, chol = _lda_result(dim, D, remove_offset, want_cholesky)
+    _tcheck(lib().kctc_lda_estimate_from_stats(zero.ctypes.data, first.ctypes.data, second.ctypes.data, D, C, int(dim),
+                                               float(within_class_factor), int(bool(remove_offset)),
+                                               float(max_singular_value), M.ctypes.data,
+                                               None if chol is None else chol.ctypes.data),
+            "kctc_lda_estimate_from_stats")
+    return M, chol
+
+
+class LdaStats:
+    """LdaEstimate's accumulators (acc-lda / sum-lda-accs) with the sums kept on
+    the device in fp64: accumulate() and acc_egs() run on the GPU, everything
+    else (stats, set_stats, read, write, estimate) on the host."""
+
+    def __init__(self, dim, num_classes, device=0):
+        self._h = ctypes.c_void_p()
+        self.dim, self.num_classes, self.device = int(dim), int(num_classes), int(device)
+        _tcheck(lib().kctc_lda_create(ctypes.byref(self._h), self.dim, self.num_classes, self.device),
+                "kctc_lda_create")
+
+    def close(self):
+        if self._h:
+            lib().kctc_lda_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def accumulate(self, feats, classes, weights=None, stream=None):
+        """feats [R][dim] float32, classes [R] int32 (id < 0: the row is skipped
+        and may hold anything), weights [R] float32 or None: device tensors,
+        contiguous.  Stream-ordered on `stream` (default: torch's current one)."""
+        import torch
+        for t, dt, what in ((feats, torch.float32, "feats"), (classes, torch.int32, "classes"),
+                            (weights, torch.float32, "weights")):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous()):
+                raise ValueError(f"LdaStats.accumulate: {what} must be a contiguous {dt} device tensor")
+        R = int(classes.shape[0])
+        if tuple(feats.shape) != (R, self.dim) or (weights is not None and tuple(weights.shape) != (R,)):
+            raise ValueError("LdaStats.accumulate: feats [R][dim], classes [R], weights [R]")
+        _tcheck(lib().kctc_lda_accumulate(self._h, _stream_handle(stream), _ptr(feats), _ptr(classes), _ptr(weights), R),
+                "kctc_lda_accumulate")
+
+    def stats(self):
+        """(zero [C], first [C][dim], second [dim][dim]) as float64; second is the
+        full, exactly symmetric matrix.  Waits for the accumulate calls so far."""
+        z = np.empty(self.num_classes, np.float64)
+        f = np.empty((self.num_classes, self.dim), np.float64)
+        s = np.empty((self.dim, self.dim), np.float64)
+        _tcheck(lib().kctc_lda_get_stats(self._h, z.ctypes.data, f.ctypes.data, s.ctypes.data), "kctc_lda_get_stats")
+        return z, f, s
+
+    def set_stats(self, zero, first, second, add=False):
+        z = _f64(zero, (self.num_classes,), "zero")
+        f = _f64(first, (self.num_classes, self.dim), "first")
+        s = _f64(second, (self.dim, self.dim), "second")
+        _tcheck(lib().kctc_lda_set_stats(self._h, z.ctypes.data, f.ctypes.data, s.ctypes.data, int(bool(add))),
+                "kctc_lda_set_stats")
+
+    def write(self, path, binary=True):
+        """LdaEstimate::Write: the file acc-lda writes (float, therefore lossy)."""
+        _tcheck(lib().kctc_lda_write(self._h, str(path).encode(), int(bool(binary))), "kctc_lda_write")
+
+    def read(self, path, add=False):
+        """LdaEstimate::Read; add=True adds the file's statistics (sum-lda-accs)."""
+        _tcheck(lib().kctc_lda_read(self._h, str(path).encode(), int(bool(add))), "kctc_lda_read")
+
+    def acc_egs(self, egs_rspecifier, ali_rspecifier, context=(0,), blank_policy="skip"):
+        """acc-lda over an egs archive and the alignment table Nnet.align_egs
+        writes (kctc_lda_acc_egs) -> (examples used, examples without an
+        alignment, mismatches, frames accumulated)."""
+        ctx = np.ascontiguousarray(context, dtype=np.int32)
+        policy = _LDA_POLICY[blank_policy] if isinstance(blank_policy, str) else int(blank_policy)
+        out = [ctypes.c_long() for _ in range(4)]
+        _tcheck(lib().kctc_lda_acc_egs(self._h, str(egs_rspecifier).encode(), str(ali_rspecifier).encode(),
+                                       ctx.ctypes.data, ctx.size, policy, *[ctypes.byref(o) for o in out]),
+                "kctc_lda_acc_egs")
+        return tuple(o.value for o in out)
+
+    def estimate(self, dim=-1, within_class_factor=0.001, remove_offset=True, max_singular_value=5.0):
+        """nnet-get-feature-transform -> (M float32 [dim][D (+1)], Cholesky factor
+        of the within-class covariance, lower-triangular float64)."""
+        if dim > self.dim:
+            raise KctcError("kctc_lda_estimate: output dimension above the feature dimension")
+        M, chol = _lda_result(dim, self.dim, remove_offset, True)
+        _tcheck(lib().kctc_lda_estimate(self._h, int(dim), float(within_class_factor), int(bool(remove_offset)),
+                                        float(max_singular_value), M.ctypes.data, chol.ctypes.data),
+                "kctc_lda_estimate")
+        return M, chol
+
+    @staticmethod
+    def _test_batch_rows(rows):
+        """Test hook (csrc/test_hooks.h): the spliced rows after which acc_egs hands
+        a batch to accumulate, rows <= 0 for the default; returns the previous value."""
+        return lib().kctc_lda_test_batch_rows(int(rows))
+
+    def guards_intact(self):
+        """Test hook (csrc/test_hooks.h): the guard words around the device arrays are untouched."""
+        ok = ctypes.c_int()
+        _tcheck(lib().kctc_lda_test_guards(self._h, ctypes.byref(ok)), "kctc_lda_test_guards")
+        return bool(ok.value)

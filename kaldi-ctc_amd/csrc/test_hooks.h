@@ -87,6 +87,15 @@ int kctc_test_rec_plan(int mode, int prec, int H, int dirs, int N, int fwd, long
  * [2][dirs][nw H] floats as bits (DX, then the GRU's E; max over all frames of
  * |value|).  -1 on error.  Nothing is launched. */
 long kctc_test_rnn_colmax_offset(int mode, int prec, int D, int H, int dirs, int T, int N);
+/* LDA statistics (kaldi_lda.h).  lda is a kctcLda_t.  test_guards: *intact = 1
+ * when the guard words around the device accumulators and the workspace are as
+ * they were written (1 too before anything is allocated); waits for the
+ * handle's work.  test_batch_rows: the spliced rows after which
+ * kctc_lda_acc_egs hands a batch to accumulate (rows <= 0: the default, 8192);
+ * returns the previous value. */
+int kctc_lda_test_guards(void *lda, int *intact);
+long kctc_lda_test_batch_rows(long rows);
+
 #ifdef __cplusplus
 }
 #endif
