@@ -29,6 +29,11 @@
  *   kctc_nnet_decode / kctc_nnet_decode_egs
  *                            <- lexicon-free CTC prefix beam search of a batch /
  *                               an egs archive (an extension; no WFST)
+ *   kctc_graph_* / kctc_wfst_decode_async / kctc_nnet_decode_graph(_egs)
+ *                            <- the best path of nnet2-ctc-latgen-faster
+ *                               (src/ctcbin/nnet2-ctc-latgen-faster.cc: Viterbi
+ *                               token passing over a decoding graph with --beam
+ *                               and --max-active; no lattice)
  * Return 0 on success (kctc_last_error() describes a failure).
  */
 #ifndef KALDI_CTC_AMD_KALDI_CTC_DECODE_H_
@@ -198,6 +203,138 @@ int kctc_nnet_decode(kctcNnet_t nnet, const float *feats_dev, int T_max, int N, 
  * best-path accuracy. */
 int kctc_nnet_decode_egs(kctcNnet_t nnet, const char *egs_rspecifier, const char *hyp_wspecifier, int minibatch_size,
                          int beam, int symbols, long *num_utts, long *num_labels, long *edit_distance);
+
+/* ---- WFST decoding (kernels: csrc/wfst_decode.hip) ---------------
+ * A decoding graph is a weighted finite-state transducer in the tropical
+ * semiring: states 0..S-1, a start state, a final cost per state (+inf: not
+ * final) and arcs (src, ilabel, olabel, weight, dst).  Arc ids are the arcs'
+ * positions after a stable sort by src.  ilabel 0 is an epsilon arc (consumes
+ * no frame); ilabel i >= 1 consumes one frame and reads column col(i) =
+ * ilabel_to_col[i] of the log-likelihood row (default i - 1: "transition-id 1
+ * is blank" under a trivial transition model; otherwise the table
+ * CtcTransitionModel::TransitionIdToPdf gives).  olabel 0 emits nothing.
+ *
+ * The graph functions return 0 or non-zero with kctc_last_error(); they need
+ * no GPU.  The device image of a graph is made (one allocation, one blocking
+ * copy) by the first decode on a device and freed by kctc_graph_destroy. */
+typedef struct kctcGraphImpl *kctcGraph_t;
+
+/* Builds a graph from host arrays: final_costs [num_states], the five arc
+ * arrays [num_arcs] in any order.  ilabel_to_col: nullable, else num_ilabels
+ * ints indexed by ilabel (entry 0 unused).  Refuses, before anything else
+ * happens: a state or start index out of range, a negative label, an ilabel
+ * >= num_ilabels, a non-finite arc weight, a final cost that is NaN or -inf, a
+ * negative column, an epsilon cycle.  Computes eps_depth, the number of arcs
+ * on the longest epsilon path: the bound of the search's closure loop. */
+int kctc_graph_create(kctcGraph_t *graph, int num_states, int start, const float *final_costs, long num_arcs,
+                      const int *src, const int *ilabel, const int *olabel, const float *weight, const int *dst,
+                      const int *ilabel_to_col, int num_ilabels);
+
+/* OpenFst text form (what fstprint writes without symbol tables): arc lines
+ * "src dst ilabel olabel [weight]", final lines "state [weight]", a missing
+ * weight is 0, the start state is the source of the first line, labels are
+ * integers.  num_states = the highest state named + 1.  Binary .fst files are
+ * not read.  kctc_graph_write_text writes the start state's lines first and
+ * weights with 9 digits, so that reading the file back gives the same graph
+ * with the same arc ids. */
+int kctc_graph_read_text(kctcGraph_t *graph, const char *path, const int *ilabel_to_col, int num_ilabels);
+int kctc_graph_write_text(kctcGraph_t graph, const char *path);
+
+/* Outputs (nullable): states, arcs, eps_depth, the highest ilabel and the
+ * highest column an emitting arc reads (-1: no emitting arc). */
+int kctc_graph_info(kctcGraph_t graph, int *num_states, long *num_arcs, int *eps_depth, int *max_ilabel,
+                    int *max_col);
+
+/* The graph as it is stored (nullable outputs): start, final_costs
+ * [num_states] and the arcs in arc-id order, [num_arcs] each. */
+int kctc_graph_get(kctcGraph_t graph, int *start, float *final_costs, int *src, int *ilabel, int *olabel,
+                   float *weight, int *dst);
+
+int kctc_graph_destroy(kctcGraph_t graph);
+
+/* Viterbi token passing, one utterance per workgroup.  Per utterance, with
+ * ac(t, i) = -acoustic_scale * loglikes[t][n][col(i)]:
+ *   a token set holds at most one token per state; a candidate replaces a
+ *   token only if (cost, arc id) is lexicographically smaller (the start
+ *   token: arc id -1);
+ *   closure(Q) relaxes every epsilon arc to the fixed point, nothing pruned;
+ *   Q_0 = closure({start: 0});
+ *   frame t: best = min cost of Q_t; E_t = the first min(max_active, count)
+ *   tokens of {cost <= best + beam} in (cost, state id) order (exact);
+ *   Q_{t+1} = closure(emit(E_t)), every emitting arc of every token of E_t
+ *   relaxed with cost + weight + ac(t, ilabel), nothing pruned;
+ *   after T frames: the token of Q_T with the smallest cost + final cost over
+ *   final states (status 1); if none is final the token of smallest cost
+ *   (status 0); Q_T empty: status -1; more than pool_tokens back-pointer
+ *   records (one per token of every Q_t, t = 0..T): status -2.  A negative
+ *   status gives words_len 0, ali -1, score +inf and leaves the other
+ *   utterances alone.  T = 0 evaluates Q_0.
+ * Costs are fp32 relative to a per-utterance fp64 offset that takes each
+ * frame's best; the selection compares those fp32 values.  A candidate whose
+ * cost is NaN or infinite starts no token.
+ *
+ * loglikes [maxT][N][num_columns] floats, device, time-major, maxT =
+ * max(input_lengths); rows t >= input_lengths[n] are never read.
+ * input_lengths: host, >= 0.  beam > 0 (+inf allowed), 1 <= max_active <= 2^20,
+ * 1 <= pool_tokens < 2^31 - 2.  Outputs, device:
+ *   words     [N][maxT + W] ints, W = (maxT + 1) * eps_depth: the non-zero
+ *             olabels of the path in order, then -1 (a path has T emitting arcs
+ *             and at most eps_depth epsilon arcs before, between and behind them)
+ *   words_len [N];  ali [maxT][N]: the ilabel of frame t's arc, -1 for t >= T
+ *   scores    [N] doubles: graph + acoustic + final cost;  status [N]
+ * workspace: kctc_wfst_decode_workspace_size bytes =
+ *   N * (52 * num_states + 4 * (maxT + 2) + 8 * pool_tokens) + at most
+ *   4096 + 2592 * N of descriptors and alignment.
+ * Returns 0, or 2 (the value of CTC_STATUS_INVALID_VALUE) with nothing
+ * enqueued for a null pointer, a negative length, a column >= num_columns, a
+ * parameter out of range; 1 / 3 for a failed copy / launch; 4 for an exception
+ * (the graph's device image could not be made: kctc_last_error()).  Asynchronous: it
+ * never synchronises the stream and allocates nothing, except that the first
+ * decode of a graph on a device makes the graph's device image.  Two calls on
+ * the same inputs give identical bytes in all five outputs. */
+int kctc_wfst_decode_workspace_size(kctcGraph_t graph, const int *input_lengths, int minibatch, int max_active,
+                                    long pool_tokens, size_t *size_bytes);
+int kctc_wfst_decode_async(kctcGraph_t graph, const float *loglikes, const int *input_lengths, int num_columns,
+                           int minibatch, float acoustic_scale, float beam, int max_active, long pool_tokens,
+                           int *words_dev, int *words_len_dev, int *ali_dev, double *scores_dev, int *status_dev,
+                           void *workspace, struct ihipStream_t *stream);
+
+/* What the last kctc_wfst_decode_async on `workspace` did, per utterance
+ * (host arrays of `minibatch` longs): expanded = the sum over its frames of
+ * |E_t|, held = the sum over t = 0..T of |Q_t| (the back-pointer records it
+ * used).  Copies from the workspace on `stream` and synchronises it. */
+int kctc_wfst_decode_counts(const void *workspace, int minibatch, struct ihipStream_t *stream, long *expanded,
+                            long *held);
+
+/* nnet2-ctc-latgen-faster's best path for a batch.  feats_dev, T_max, N,
+ * num_frames as for kctc_nnet_propagate_seq (N <= 64): the variable-length
+ * forward, a softmax if the network does not end in one, then on the device
+ * (log(max(p, 1e-10)) - log prior) * prob_scale with the model's priors (none
+ * if the model has none) and all frames kept, then kctc_wfst_decode_async on
+ * the network's stream with acoustic_scale.  prob_scale is
+ * CtcDecodableAmNnet's scale of the log-likelihoods, acoustic_scale the
+ * decoder's own; the reference uses one of them and leaves the other at 1.
+ * pool_tokens <= 0: (T_max + 1) * min(num_states, 4 * max_active + 4096).  Outputs,
+ * host: words_host [N][words_stride] (the first min(words_len, words_stride)
+ * words of each path, then -1), words_len_host [N], ali_host [T_max][N] (-1
+ * for t >= num_frames[n]), scores_host [N], status_host [N]. */
+int kctc_nnet_decode_graph(kctcNnet_t nnet, kctcGraph_t graph, const float *feats_dev, int T_max, int N,
+                           const int *num_frames, float prob_scale, float acoustic_scale, float beam, int max_active,
+                           long pool_tokens, int *words_host, int words_stride, int *words_len_host, int *ali_host,
+                           double *scores_host, int *status_host);
+
+/* Decodes every example of an egs archive (read as kctc_nnet_decode_egs reads
+ * it) and writes, per example key, the words as a Kaldi Int32Vector to a binary
+ * "ark:" (Kaldi's words.tra as a table) and, if ali_wspecifier is not null,
+ * the per-frame ilabels to a second one.  Utterances with a negative status
+ * are counted and not written.  Outputs (nullable): utterances decoded
+ * (status >= 0), how many of them reached a final state, utterances that
+ * failed, the sum of the decoded utterances' scores and of their frames. */
+int kctc_nnet_decode_graph_egs(kctcNnet_t nnet, kctcGraph_t graph, const char *egs_rspecifier,
+                               const char *words_wspecifier, const char *ali_wspecifier, int minibatch_size,
+                               float prob_scale, float acoustic_scale, float beam, int max_active, long pool_tokens,
+                               long *num_done, long *num_final, long *num_failed, double *tot_score,
+                               long *tot_frames);
 
 #ifdef __cplusplus
 }

@@ -265,6 +265,252 @@ def ctc_beam_search(acts, input_lengths, beam=16, symbols=40, blank=0, stream=No
     return [hyp[n * max_t:n * max_t + int(hyp_len[n])].tolist() for n in range(N)], scores.cpu().numpy()
 
 
+class Graph:
+    """A decoding graph (kctcGraph_t, include/kaldi_ctc_decode.h): a weighted
+    finite-state transducer in the tropical semiring.  final_costs [S] (+inf:
+    not final); src, ilabel, olabel, weight, dst: one entry per arc, any order
+    (arc ids are the positions after a stable sort by src).  ilabel 0 is an
+    epsilon arc; ilabel i >= 1 reads column ilabel_to_col[i] (default i - 1).
+    Creation validates on the host and needs no GPU."""
+
+    def __init__(self, final_costs=None, src=(), ilabel=(), olabel=(), weight=(), dst=(), start=0,
+                 ilabel_to_col=None, _handle=None):
+        self.h = None
+        if _handle is not None:
+            self.h = _handle
+            return
+        fin = np.ascontiguousarray(final_costs, dtype=np.float32)
+        arrs = [np.ascontiguousarray(x, dtype=np.int32) for x in (src, ilabel, olabel, dst)]
+        w = np.ascontiguousarray(weight, dtype=np.float32)
+        if fin.ndim != 1 or any(x.ndim != 1 or x.size != w.size for x in arrs) or w.ndim != 1:
+            raise KctcError("Graph: final_costs and the five arc arrays must be 1-D, the arc arrays of one length")
+        col = None if ilabel_to_col is None else np.ascontiguousarray(ilabel_to_col, dtype=np.int32)
+        h = ctypes.c_void_p()
+        _tcheck(lib().kctc_graph_create(ctypes.byref(h), fin.size, int(start), fin.ctypes.data, w.size,
+                                        arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data, w.ctypes.data,
+                                        arrs[3].ctypes.data, None if col is None else col.ctypes.data,
+                                        0 if col is None else col.size), "graph_create")
+        self.h = h
+
+    @classmethod
+    def read_text(cls, path, ilabel_to_col=None):
+        """OpenFst text form (fstprint without symbol tables)."""
+        col = None if ilabel_to_col is None else np.ascontiguousarray(ilabel_to_col, dtype=np.int32)
+        h = ctypes.c_void_p()
+        _tcheck(lib().kctc_graph_read_text(ctypes.byref(h), str(path).encode(),
+                                           None if col is None else col.ctypes.data,
+                                           0 if col is None else col.size), "graph_read_text")
+        return cls(_handle=h)
+
+    def write_text(self, path):
+        _tcheck(lib().kctc_graph_write_text(self.h, str(path).encode()), "graph_write_text")
+
+    def info(self):
+        """dict(num_states, num_arcs, eps_depth, max_ilabel, max_col)"""
+        s, d, il, c, a = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_long()
+        _tcheck(lib().kctc_graph_info(self.h, ctypes.byref(s), ctypes.byref(a), ctypes.byref(d), ctypes.byref(il),
+                                      ctypes.byref(c)), "graph_info")
+        return dict(num_states=s.value, num_arcs=a.value, eps_depth=d.value, max_ilabel=il.value, max_col=c.value)
+
+    @property
+    def num_states(self):
+        return self.info()["num_states"]
+
+    @property
+    def num_arcs(self):
+        return self.info()["num_arcs"]
+
+    @property
+    def eps_depth(self):
+        return self.info()["eps_depth"]
+
+    def arrays(self):
+        """The stored graph: dict(start, final_costs, src, ilabel, olabel, weight,
+        dst), the arcs in arc-id order."""
+        i = self.info()
+        S, NA = i["num_states"], i["num_arcs"]
+        start = ctypes.c_int()
+        fin = np.empty(S, np.float32)
+        a = {k: np.empty(NA, np.int32) for k in ("src", "ilabel", "olabel", "dst")}
+        w = np.empty(NA, np.float32)
+        _tcheck(lib().kctc_graph_get(self.h, ctypes.byref(start), fin.ctypes.data, a["src"].ctypes.data,
+                                     a["ilabel"].ctypes.data, a["olabel"].ctypes.data, w.ctypes.data,
+                                     a["dst"].ctypes.data), "graph_get")
+        return dict(start=start.value, final_costs=fin, weight=w, **a)
+
+    def close(self):
+        if self.h is not None:
+            lib().kctc_graph_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ctc_token_graph(A, blank=0):
+    """The lexicon-free CTC label loop over A columns as a Graph: state 0 (start)
+    is "after a blank or nothing", one state per label is "inside that label".
+    ilabel = column + 1; entering a label emits it (olabel = the column when
+    blank is 0, which is the project's symbol id, else column + 1); repeating
+    it and blank emit nothing.  Every state is final.  Its best path is the
+    collapsed frame-wise argmax."""
+    if A < 2 or not 0 <= blank < A:
+        raise KctcError("ctc_token_graph: need A >= 2 and a blank inside [0, A)")
+    labels = [c for c in range(A) if c != blank]
+    state = {c: 1 + k for k, c in enumerate(labels)}
+    src, il, ol, dst = [], [], [], []
+    for s in range(A):
+        src.append(s); il.append(blank + 1); ol.append(0); dst.append(0)
+        for c in labels:
+            same = state[c] == s
+            src.append(s); il.append(c + 1); ol.append(0 if same else (c if blank == 0 else c + 1)); dst.append(state[c])
+    return Graph(np.zeros(A, np.float32), src, il, ol, np.zeros(len(src), np.float32), dst)
+
+
+def ctc_lexicon_graph(lexicon, A, word_costs=None, blank=0):
+    """A pronunciation trie composed with the CTC topology, as a Graph.
+    lexicon: list of (word id >= 1, [columns != blank]) pronunciations;
+    word_costs: None or one cost per entry.  It accepts exactly the frame label
+    sequences whose CTC collapse is a concatenation of pronunciations.  Every
+    trie node v has a state L(v) "inside v's label" (loops on that label) and a
+    state B(v) "behind a blank inside the word".  A word ends on an epsilon arc
+    (olabel = the word id, weight = its cost) from L(v) to the root copy
+    R[label of v], which has the root's arcs except the one on that label: a
+    word that starts with the label the last one ended on needs a blank first,
+    which leads from R[x] to the root R.  R and every R[x] are final."""
+    if A < 2 or not 0 <= blank < A:
+        raise KctcError("ctc_lexicon_graph: need A >= 2 and a blank inside [0, A)")
+    costs = [0.0] * len(lexicon) if word_costs is None else [float(c) for c in word_costs]
+    if len(costs) != len(lexicon):
+        raise KctcError("ctc_lexicon_graph: one cost per lexicon entry")
+    children = [{}]  # trie: node -> {column: node}; node 0 is the root
+    label = [-1]
+    ends = [[]]
+    for k, (word, pron) in enumerate(lexicon):
+        if int(word) < 1 or len(pron) == 0 or any(not 0 <= c < A or c == blank for c in pron):
+            raise KctcError(f"ctc_lexicon_graph: entry {k} needs a word id >= 1 and columns in [0, A) other than blank")
+        v = 0
+        for c in pron:
+            c = int(c)
+            if c not in children[v]:
+                children[v][c] = len(children)
+                children.append({})
+                label.append(c)
+                ends.append([])
+            v = children[v][c]
+        ends[v].append((int(word), costs[k]))
+    nodes = len(children)
+    used = sorted({label[v] for v in range(1, nodes) if ends[v]})
+    root_copy = {x: 1 + k for k, x in enumerate(used)}  # R[x]; the root R is state 0
+    base = 1 + len(used)
+    L = lambda v: base + 2 * (v - 1)
+    B = lambda v: base + 2 * (v - 1) + 1
+    src, il, ol, w, dst = [], [], [], [], []
+
+    def arc(s, i, o, c, d):
+        src.append(s); il.append(i); ol.append(o); w.append(c); dst.append(d)
+
+    arc(0, blank + 1, 0, 0.0, 0)
+    for c, v in sorted(children[0].items()):
+        arc(0, c + 1, 0, 0.0, L(v))
+    for x, r in root_copy.items():
+        arc(r, blank + 1, 0, 0.0, 0)
+        for c, v in sorted(children[0].items()):
+            if c != x:
+                arc(r, c + 1, 0, 0.0, L(v))
+    for v in range(1, nodes):
+        arc(L(v), label[v] + 1, 0, 0.0, L(v))
+        arc(L(v), blank + 1, 0, 0.0, B(v))
+        arc(B(v), blank + 1, 0, 0.0, B(v))
+        for c, u in sorted(children[v].items()):
+            if c != label[v]:
+                arc(L(v), c + 1, 0, 0.0, L(u))
+            arc(B(v), c + 1, 0, 0.0, L(u))
+        for word, cost in ends[v]:
+            arc(L(v), 0, word, cost, root_copy[label[v]])
+    S = base + 2 * (nodes - 1)
+    fin = np.full(S, np.inf, np.float32)
+    fin[:base] = 0.0
+    return Graph(fin, src, il, ol, w, dst)
+
+
+def wfst_decode_workspace_size(graph, input_lengths, max_active, pool_tokens):
+    il = np.ascontiguousarray(input_lengths, dtype=np.int32)
+    out = ctypes.c_size_t()
+    st = lib().kctc_wfst_decode_workspace_size(graph.h, il.ctypes.data, len(il), int(max_active), int(pool_tokens),
+                                               ctypes.byref(out))
+    if st != 0:
+        raise CtcError(st, "kctc_wfst_decode_workspace_size")
+    return out.value
+
+
+def wfst_decode_counts(workspace, N, stream=None):
+    """Per utterance of the last wfst_decode on `workspace`: (sum over the
+    frames of |E_t|, sum over t = 0..T of |Q_t|) as two np.int64 [N]
+    (kctc_wfst_decode_counts; synchronises the stream)."""
+    e, q = np.zeros(N, np.int64), np.zeros(N, np.int64)
+    _tcheck(lib().kctc_wfst_decode_counts(workspace.data_ptr(), int(N), _stream_handle(stream), e.ctypes.data,
+                                          q.ctypes.data), "wfst_decode_counts")
+    return e, q
+
+
+def wfst_default_pool_tokens(graph, max_T, max_active):
+    """Back-pointer records per utterance when the caller names none: room for
+    min(num_states, 4 * max_active + 4096) tokens in every one of the max_T + 1
+    token sets (a token set holds what max_active tokens reach over one
+    emitting arc and the epsilon arcs behind it)."""
+    return (int(max_T) + 1) * min(graph.num_states, 4 * int(max_active) + 4096)
+
+
+def wfst_decode(loglikes, input_lengths, graph, beam=15.0, max_active=7000, acoustic_scale=1.0, pool_tokens=None,
+                stream=None, workspace=None):
+    """Viterbi token passing over `graph` (kctc_wfst_decode_async) for a torch
+    CUDA tensor loglikes [T, N, A] (float32, time-major; rows behind an
+    utterance's length are never read).  Returns (words: list of N int lists,
+    the non-zero olabels of the best path; ali np.int32 [T, N]: the ilabel of
+    every frame, -1 behind the utterance; scores np.float64 [N]: graph +
+    acoustic + final cost; status np.int32 [N]: 1 a final state was reached,
+    0 none was (best token, no final cost), -1 no token survived, -2 more than
+    pool_tokens back-pointer records; a negative status gives no words, ali
+    -1 and score +inf)."""
+    import torch
+    assert loglikes.is_cuda and loglikes.dtype == torch.float32 and loglikes.is_contiguous()
+    T, N, A = loglikes.shape
+    il = np.ascontiguousarray(input_lengths, dtype=np.int32)
+    if len(il) != N or (N and int(il.max()) > T):
+        raise CtcError(2, "wfst_decode")
+    if loglikes.numel() == 0:  # only utterances without frames: the call still wants a device pointer
+        loglikes = torch.zeros(1, dtype=torch.float32, device=loglikes.device)
+    max_t = int(il.max()) if N else 0
+    if pool_tokens is None:
+        pool_tokens = wfst_default_pool_tokens(graph, max_t, max_active)
+    if workspace is None:
+        workspace = torch.empty(wfst_decode_workspace_size(graph, il, max_active, pool_tokens), dtype=torch.uint8,
+                                device=loglikes.device)
+    row = max_t + (max_t + 1) * graph.eps_depth
+    words = torch.empty((N, max(row, 1)), dtype=torch.int32, device=loglikes.device)
+    words_len = torch.empty(N, dtype=torch.int32, device=loglikes.device)
+    ali = torch.empty((max(max_t, 1), N), dtype=torch.int32, device=loglikes.device)
+    scores = torch.empty(N, dtype=torch.float64, device=loglikes.device)
+    status = torch.empty(N, dtype=torch.int32, device=loglikes.device)
+    st = lib().kctc_wfst_decode_async(graph.h, loglikes.data_ptr(), il.ctypes.data, A, N, float(acoustic_scale),
+                                      float(beam), int(max_active), int(pool_tokens), words.data_ptr(),
+                                      words_len.data_ptr(), ali.data_ptr(), scores.data_ptr(), status.data_ptr(),
+                                      workspace.data_ptr(), _stream_handle(stream))
+    if st != 0:
+        raise CtcError(st, "kctc_wfst_decode_async")
+    if stream is not None:
+        torch.cuda.synchronize()  # the copies below run on the current stream
+    words, words_len = words.cpu().numpy(), words_len.cpu().numpy()
+    ali_out = np.full((T, N), -1, np.int32)
+    ali_out[:max_t] = ali.cpu().numpy()[:max_t]
+    return ([words[n, :int(words_len[n])].tolist() for n in range(N)], ali_out, scores.cpu().numpy(),
+            status.cpu().numpy())
+
+
 def read_int_vector_ark(path):
     """Binary Kaldi archive of Int32Vector (what Nnet.align_egs writes and
     ali-to-post reads) -> dict key -> np.int32 array, in archive order."""
@@ -974,6 +1220,48 @@ class Nnet:
                                            int(minibatch_size), int(beam), int(symbols), ctypes.byref(nu),
                                            ctypes.byref(nl), ctypes.byref(ed)), "nnet_decode_egs")
         return nu.value, nl.value, ed.value
+
+    def decode_graph(self, feats, T, N, num_frames, graph, beam=15.0, max_active=7000, prob_scale=1.0,
+                     acoustic_scale=1.0, pool_tokens=None):
+        """The best path of nnet2-ctc-latgen-faster for a variable-length batch
+        (kctc_nnet_decode_graph; feats as for train_step, N <= 64, every
+        utterance as if run alone): the forward, (log(max(p, 1e-10)) - log
+        prior) * prob_scale on the device, then wfst_decode over `graph` ->
+        (words: list of N int lists, ali np.int32 [T, N], scores np.float64 [N],
+        status np.int32 [N]) as wfst_decode returns them."""
+        self._check_feats(feats, T, N)
+        nf = np.ascontiguousarray(num_frames, dtype=np.int32)
+        if len(nf) != N:
+            raise KctcError("decode_graph: num_frames must have N entries")
+        row = max(T + (T + 1) * graph.eps_depth, 1)
+        words = np.empty((N, row), np.int32)
+        words_len = np.empty(N, np.int32)
+        ali = np.empty((T, N), np.int32)
+        scores = np.empty(N, np.float64)
+        status = np.empty(N, np.int32)
+        _tcheck(lib().kctc_nnet_decode_graph(self.h, graph.h, _ptr(feats), T, N, nf.ctypes.data, prob_scale,
+                                             acoustic_scale, beam, int(max_active),
+                                             0 if pool_tokens is None else int(pool_tokens), words.ctypes.data, row,
+                                             words_len.ctypes.data, ali.ctypes.data, scores.ctypes.data,
+                                             status.ctypes.data), "nnet_decode_graph")
+        return [words[n, :words_len[n]].tolist() for n in range(N)], ali, scores, status
+
+    def decode_graph_egs(self, rspecifier, words_wspecifier, graph, ali_wspecifier=None, minibatch_size=16,
+                         beam=15.0, max_active=7000, prob_scale=1.0, acoustic_scale=1.0, pool_tokens=None):
+        """Decodes every example of an egs archive over `graph` and writes the
+        words per key as the Int32Vector table `words_wspecifier` (Kaldi's
+        words.tra as a table) and, if named, the per-frame ilabels to
+        `ali_wspecifier` (kctc_nnet_decode_graph_egs) -> dict(num_done,
+        num_final, num_failed, tot_score, tot_frames); utterances with a
+        negative status are counted in num_failed and not written."""
+        nd, nfin, nfail, fr, sc = ctypes.c_long(), ctypes.c_long(), ctypes.c_long(), ctypes.c_long(), ctypes.c_double()
+        _tcheck(lib().kctc_nnet_decode_graph_egs(
+            self.h, graph.h, str(rspecifier).encode(), str(words_wspecifier).encode(),
+            None if ali_wspecifier is None else str(ali_wspecifier).encode(), int(minibatch_size), prob_scale,
+            acoustic_scale, beam, int(max_active), 0 if pool_tokens is None else int(pool_tokens), ctypes.byref(nd),
+            ctypes.byref(nfin), ctypes.byref(nfail), ctypes.byref(sc), ctypes.byref(fr)), "nnet_decode_graph_egs")
+        return dict(num_done=nd.value, num_final=nfin.value, num_failed=nfail.value, tot_score=sc.value,
+                    tot_frames=fr.value)
 
     def adjust_priors(self, posterior_sum=None, google_prior_const=0.0):
         """nnet-adjust-priors: priors = posterior_sum / its total, or (with

@@ -1,7 +1,8 @@
 // infer_api.cpp -- C ABI of include/kaldi_ctc_decode.h and the forward-only
 // entry points of kaldi_ctc_train.h: propagate, the CTC decodable (one
 // utterance and batched), posterior sums, priors, compute-prob, and the CTC
-// forced alignment and prefix beam search of a batch or an egs archive.
+// forced alignment, prefix beam search and graph search of a batch or an egs
+// archive.
 #include "kaldi_ctc_decode.h"
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "kaldi_io.h"
 #include "nnet_handle.h"
 #include "seq_align.h"
+#include "wfst_decode.h"
 
 using kctc::nnet2::CuDevice;
 
@@ -186,6 +188,175 @@ int kctc_nnet_decode_egs(kctcNnet_t n, const char *egs_rspecifier, const char *h
     if (num_utts) *num_utts = utts;
     if (num_labels) *num_labels = labels;
     if (edit_distance) *edit_distance = errs;
+  });
+}
+
+}  // extern "C"
+
+// kctc_nnet_decode_graph on a formatted input: variable-length forward, the
+// decodable rows of every utterance (all frames kept, utterance after
+// utterance), then the graph search on the network's stream
+struct GraphDecodeOpts {
+  float prob_scale, acoustic_scale, beam;
+  int max_active;
+  long pool_tokens;
+};
+static void decode_graph_batch(kctcNnet_t n, kctcGraph_t g, const float *feats_dev, int T_max, int N,
+                               const int *num_frames, const GraphDecodeOpts &opt, int *words_host, int words_stride,
+                               int *words_len_host, int *ali_host, double *scores_host, int *status_host) {
+  KCTC_REQUIRE(N >= 1 && N <= kctc::kSeqMaxN, "kctc_nnet_decode_graph: N outside [1, 64]");
+  KCTC_REQUIRE(words_stride >= 1, "kctc_nnet_decode_graph: words_stride < 1");
+  kctc::SeqLens lens;
+  KCTC_REQUIRE(kctc::seq_lens(num_frames, T_max, N, &lens), "kctc_nnet_decode_graph: num_frames outside [1, T_max]");
+  const auto &o = n->evaluator.ForwardSeq(feats_dev, T_max, N, num_frames);
+  const int A = o.NumCols(), C = n->nnet.NumComponents();
+  const float *probs = o.Data();
+  if (!dynamic_cast<const kctc::nnet2::SoftmaxComponent *>(&n->nnet.GetComponent(C - 1))) {
+    n->wfst_probs.ensure(sizeof(float) * (size_t)T_max * N * A);
+    kctc::softmax_rows(n->stream, o.Data(), (long)T_max * N, A, n->wfst_probs.f());
+    probs = n->wfst_probs.f();
+  }
+  const float *pd = device_priors(n, A);
+  long total = 0;
+  int maxT = 0;
+  std::vector<long long> ll_off((size_t)N), ll_stride((size_t)N, A);
+  for (int u = 0; u < N; u++) {
+    ll_off[u] = total * A;
+    total += num_frames[u];
+    maxT = std::max(maxT, num_frames[u]);
+  }
+  n->dec_out.ensure(sizeof(float) * (size_t)total * A);
+  n->dec_scratch.ensure(kctc::seq_decodable_scratch_bytes(T_max, N));
+  n->dec_kept.ensure(sizeof(int) * kctc::kSeqMaxN);
+  // blank_threshold 1: no frame is dropped, utterance u's rows start at row sum(num_frames[< u])
+  kctc::seq_decodable(n->stream, probs, T_max, N, A, lens, pd, opt.prob_scale, 1.0f, 1.0e-10f, n->dec_out.f(),
+                      n->dec_scratch.p, static_cast<int *>(n->dec_kept.p));
+  int S = 0, depth = 0;
+  if (kctc_graph_info(g, &S, nullptr, &depth, nullptr, nullptr)) throw std::runtime_error(kctc_last_error());
+  const long pool = opt.pool_tokens > 0 ? opt.pool_tokens
+                                        : ((long)T_max + 1) * std::min<long>(S, 4l * std::max(opt.max_active, 1) + 4096);
+  const size_t ws = kctc::wfst::decode_workspace_bytes(g, num_frames, N, opt.max_active, pool);
+  KCTC_REQUIRE(ws > 0, "kctc_nnet_decode_graph: max_active or pool_tokens out of range");
+  const size_t row = (size_t)maxT + (size_t)kctc::wfst::words_slack(depth, maxT);
+  n->wfst_ws.ensure(ws);
+  n->wfst_words.ensure(sizeof(int) * row * N);
+  n->wfst_len.ensure(sizeof(int) * N);
+  n->wfst_ali.ensure(sizeof(int) * (size_t)maxT * N);
+  n->wfst_scores.ensure(sizeof(double) * N);
+  n->wfst_status.ensure(sizeof(int) * N);
+  const int st = kctc::wfst::decode_strided(
+      g, n->dec_out.f(), num_frames, ll_off.data(), ll_stride.data(), A, N, opt.acoustic_scale, opt.beam,
+      opt.max_active, pool, static_cast<int *>(n->wfst_words.p), static_cast<int *>(n->wfst_len.p),
+      static_cast<int *>(n->wfst_ali.p), static_cast<double *>(n->wfst_scores.p), static_cast<int *>(n->wfst_status.p),
+      n->wfst_ws.p, n->stream);
+  if (st == 2)
+    throw std::invalid_argument("kctc_wfst_decode_async: invalid value (beam, max_active, pool_tokens, or the graph "
+                                "reads a column the network does not output)");
+  if (st) throw std::runtime_error("kctc_wfst_decode_async failed");
+  std::fill(words_host, words_host + (size_t)words_stride * N, -1);
+  std::fill(ali_host, ali_host + (size_t)T_max * N, -1);
+  const size_t wcopy = std::min<size_t>(row, (size_t)words_stride);
+  KCTC_HIP_CHECK(hipMemcpy2DAsync(words_host, sizeof(int) * words_stride, n->wfst_words.p, sizeof(int) * row,
+                                  sizeof(int) * wcopy, N, hipMemcpyDeviceToHost, n->stream));
+  KCTC_HIP_CHECK(hipMemcpyAsync(ali_host, n->wfst_ali.p, sizeof(int) * (size_t)maxT * N, hipMemcpyDeviceToHost,
+                                n->stream));
+  KCTC_HIP_CHECK(hipMemcpyAsync(words_len_host, n->wfst_len.p, sizeof(int) * N, hipMemcpyDeviceToHost, n->stream));
+  KCTC_HIP_CHECK(hipMemcpyAsync(scores_host, n->wfst_scores.p, sizeof(double) * N, hipMemcpyDeviceToHost, n->stream));
+  KCTC_HIP_CHECK(hipMemcpyAsync(status_host, n->wfst_status.p, sizeof(int) * N, hipMemcpyDeviceToHost, n->stream));
+  KCTC_HIP_CHECK(hipStreamSynchronize(n->stream));
+}
+
+extern "C" {
+
+int kctc_nnet_decode_graph(kctcNnet_t n, kctcGraph_t g, const float *feats_dev, int T_max, int N,
+                           const int *num_frames, float prob_scale, float acoustic_scale, float beam, int max_active,
+                           long pool_tokens, int *words_host, int words_stride, int *words_len_host, int *ali_host,
+                           double *scores_host, int *status_host) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && g && feats_dev && num_frames && words_host && words_len_host && ali_host && scores_host &&
+                     status_host,
+                 "kctc_nnet_decode_graph: null argument");
+    n->activate();
+    decode_graph_batch(n, g, feats_dev, T_max, N, num_frames,
+                       GraphDecodeOpts{prob_scale, acoustic_scale, beam, max_active, pool_tokens}, words_host,
+                       words_stride, words_len_host, ali_host, scores_host, status_host);
+    collect_profile(n);
+  });
+}
+
+int kctc_nnet_decode_graph_egs(kctcNnet_t n, kctcGraph_t g, const char *egs_rspecifier, const char *words_wspecifier,
+                               const char *ali_wspecifier, int minibatch_size, float prob_scale, float acoustic_scale,
+                               float beam, int max_active, long pool_tokens, long *num_done, long *num_final,
+                               long *num_failed, double *tot_score, long *tot_frames) {
+  return kctc_guarded([&] {
+    KCTC_REQUIRE(n && g && egs_rspecifier && words_wspecifier, "kctc_nnet_decode_graph_egs: null argument");
+    KCTC_REQUIRE(minibatch_size >= 1 && minibatch_size <= kctc::kSeqMaxN,
+                 "kctc_nnet_decode_graph_egs: minibatch_size outside [1, 64]");
+    const std::string wpath = ark_path(words_wspecifier), apath = ali_wspecifier ? ark_path(ali_wspecifier) : "";
+    n->activate();
+    std::ofstream wos(wpath, std::ios::binary | std::ios::trunc), aos;
+    if (!wos) throw std::runtime_error("cannot write word archive " + wpath);
+    if (ali_wspecifier) {
+      aos.open(apath, std::ios::binary | std::ios::trunc);
+      if (!aos) throw std::runtime_error("cannot write alignment archive " + apath);
+    }
+    int depth = 0;
+    if (kctc_graph_info(g, nullptr, nullptr, &depth, nullptr, nullptr)) throw std::runtime_error(kctc_last_error());
+    long done = 0, fin = 0, failed = 0, frames = 0;
+    double score = 0.0;
+    std::vector<int> words, words_len, ali, status;
+    std::vector<double> scores;
+    const GraphDecodeOpts opt{prob_scale, acoustic_scale, beam, max_active, pool_tokens};
+    for_each_batch(egs_rspecifier, minibatch_size, [&](std::vector<kctc::egs::Example> &batch) {
+      // every example from its own start offset, pad_input = false (as kctc_nnet_sum_posteriors)
+      std::unique_ptr<kctc::egs::Minibatch> mb =
+          kctc::egs::pack_minibatch(batch, n->nnet.LeftContext(), n->nnet.RightContext(), true);
+      n->check_input_dim(*mb);
+      kctc::SeqLens lens;
+      if (!kctc::seq_lens(mb->num_frames.data(), mb->T_max, mb->N, &lens))
+        throw std::invalid_argument("an example is shorter than the network's context");
+      n->stage_minibatch(*mb);
+      const int N = mb->N, T_max = mb->T_max;
+      const size_t row = (size_t)T_max + (size_t)kctc::wfst::words_slack(depth, T_max);
+      KCTC_REQUIRE(row < (size_t)INT_MAX, "kctc_nnet_decode_graph_egs: the word rows are too long");
+      words.resize(row * N);
+      words_len.resize(N);
+      ali.resize((size_t)T_max * N);
+      scores.resize(N);
+      status.resize(N);
+      decode_graph_batch(n, g, n->egs_feats.f(), T_max, N, mb->num_frames.data(), opt, words.data(), (int)row,
+                         words_len.data(), ali.data(), scores.data(), status.data());
+      for (int u = 0; u < N; u++) {
+        if (status[u] < 0) {
+          failed++;
+          continue;
+        }
+        const int *w = words.data() + row * u;
+        write_int_vector_entry(wos, mb->keys[u], std::vector<int32_t>(w, w + words_len[u]));
+        const int T = mb->num_frames[u];
+        if (ali_wspecifier) {
+          std::vector<int32_t> v((size_t)T);
+          for (int t = 0; t < T; t++) v[t] = ali[(size_t)t * N + u];
+          write_int_vector_entry(aos, mb->keys[u], v);
+        }
+        done++;
+        fin += status[u] == 1 ? 1 : 0;
+        score += scores[u];
+        frames += T;
+      }
+    });
+    wos.flush();
+    if (!wos) throw std::runtime_error("error writing word archive " + wpath);
+    if (ali_wspecifier) {
+      aos.flush();
+      if (!aos) throw std::runtime_error("error writing alignment archive " + apath);
+    }
+    collect_profile(n);
+    if (num_done) *num_done = done;
+    if (num_final) *num_final = fin;
+    if (num_failed) *num_failed = failed;
+    if (tot_score) *tot_score = score;
+    if (tot_frames) *tot_frames = frames;
   });
 }
 

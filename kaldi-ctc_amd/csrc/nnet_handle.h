@@ -67,6 +67,9 @@ struct kctcNnetImpl : kctcStreams {
   kctc::nnet2::DevBuf ali_ws, ali_ids, ali_scores;
   // prefix beam search (kctc_nnet_decode): workspace, hypotheses, their lengths, scores
   kctc::nnet2::DevBuf beam_ws, beam_hyp, beam_len, beam_scores;
+  // graph search (kctc_nnet_decode_graph): posteriors of a network without a final
+  // softmax, workspace, words, their counts, frame ilabels, scores, status
+  kctc::nnet2::DevBuf wfst_probs, wfst_ws, wfst_words, wfst_len, wfst_ali, wfst_scores, wfst_status;
   // nnet2-ctc model file extras: the CtcTransitionModel exactly as read (opaque
   // bytes, in the mode of the file it came from) and AmNnet's priors
   std::string trans_model;
